@@ -12,8 +12,14 @@ RCCL all-gather of the packed tiles (16 B/px), so the image is complete on
 every rank.  Rays = cast_ray calls + is_light_blocked calls, exactly as the
 reference defines its work; counted by the kernel.
 
-Launch: python bench.py [--gpus N] [--steps K] [--warmup W]
+Launch: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+A plain run sets up, warms up, times the K steps and prints one JSON line (`ms_per_step`: the wall
+time of one timed step); `--dump-outputs DIR` also writes the last timed step's frame (rgb.npy,
+z.npy; the scene, seed and counter RNG are fixed, so two runs with the same arguments see the same
+inputs).  `--full` adds the legs that take runs of their own after the timed steps: the counting
+pass behind `roofline`, the stratified-RNG frame, every BVH builder, the postprocess leg and the
+CPU baselines (`--no-count`, `--no-post`, `--no-cpu-baseline` drop single legs of a full run).
 `--gpus N` always means N ranks: without a torchrun environment, bench.py starts
 torch.distributed.run itself (one child process per GPU, before anything touches a GPU)
 and exits with its code; under torchrun, WORLD_SIZE must equal N or it exits non-zero.
@@ -96,9 +102,18 @@ def parse():
                     help="k_shadow lanes per shade-point slot (rtx_set_option RTX_OPT_SHADOW_SLOT; 0 = automatic)")
     ap.add_argument("--shadow-grab", type=int, default=0,
                     help="k_shadow lane slots per work-queue grab (RTX_OPT_SHADOW_GRAB; 0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-count", action="store_true", help="skip the traversal-counting pass (roofline)")
-    ap.add_argument("--no-post", action="store_true", help="skip the postprocess (DoF + mist) side leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs: the traversal-counting pass (roofline), the "
+                         "stratified-RNG frame, every BVH builder, the postprocess leg and the CPU baselines; without "
+                         "it a run sets up, warms up, times the steps and prints the line (those keys are null or absent)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame, as the caller receives it on the host, to DIR/rgb.npy "
+                         "(H, W, 3) and DIR/z.npy (H, W), float32; a frame over the size limit is written as a fixed "
+                         "seeded sample of its pixels, with their row-major indices in DIR/pixel_index.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-count", action="store_true", help="with --full: skip the traversal-counting pass (roofline)")
+    ap.add_argument("--no-post", action="store_true",
+                    help="with --full: skip the stratified-RNG, BVH-builder and postprocess (DoF + mist) side legs")
     ap.add_argument("--cpu-target-s", type=float, default=12.0)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--loopback", action="store_true",
@@ -106,7 +121,35 @@ def parse():
                          "with a device-to-device copy for the RCCL gather); a one-GPU rehearsal, never a scaling number")
     ap.add_argument("--dry-run", action="store_true",
                     help="rank bring-up only (gloo, no GPU): print the ranks' world and exit (tests)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps: need at least one timed step")
+    if not a.full:  # a plain run does only what the headline figure needs
+        a.no_count = a.no_post = a.no_cpu_baseline = True
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, rgb, z, width, height):
+    """--dump-outputs: the frame of the last timed step (host float32 rgb and z, as the caller of the
+    timed path receives them) as DIR/rgb.npy and DIR/z.npy.  A frame over DUMP_LIMIT_BYTES is written
+    as a sample of its pixels chosen by a fixed seed (the same pixels in every run of that size),
+    their row-major indices beside it in DIR/pixel_index.npy (float64: exact below 2^53)."""
+    import numpy as np
+    rgb = np.asarray(rgb, dtype=np.float32).reshape(height, width, 3)
+    z = np.asarray(z, dtype=np.float32).reshape(height, width)
+    os.makedirs(dirname, exist_ok=True)
+    if rgb.nbytes + z.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(dirname, "rgb.npy"), rgb)
+        np.save(os.path.join(dirname, "z.npy"), z)
+        return
+    n = (DUMP_LIMIT_BYTES - 4096) // (12 + 4 + 8)  # rgb + z + index per pixel, room for the three headers
+    idx = np.sort(np.random.default_rng(20240607).choice(width * height, size=n, replace=False))
+    np.save(os.path.join(dirname, "rgb.npy"), rgb.reshape(-1, 3)[idx])
+    np.save(os.path.join(dirname, "z.npy"), z.reshape(-1)[idx])
+    np.save(os.path.join(dirname, "pixel_index.npy"), idx.astype(np.float64))
 
 
 def launch_mode(a):
@@ -720,6 +763,9 @@ def main():
         torch.distributed.all_reduce(rr)
         rays, closest = int(rr[0].item()), int(rr[1].item())
 
+    if a.dump_outputs and rank == 0:  # before any later leg renders again
+        dump_outputs(a.dump_outputs, h_rgb.numpy(), h_z.numpy(), a.width, a.height)
+
     kernel_ms = float(np.mean(kms))
     shadow_ms = float(np.mean(sms))
     validation = None
@@ -1012,6 +1058,8 @@ def main_group(a):
             d = g.device_stats(r)
             dev[r].append((d.kernel_ms, d.trace_ms, d.shadow_ms, d.closest_rays + d.shadow_rays))
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:  # before the counting render overwrites the host frame
+        dump_outputs(a.dump_outputs, h_rgb, h_z, a.width, a.height)
     per_dev = []
     for r in range(n):
         m = np.array(dev[r], dtype=np.float64).mean(0)

@@ -149,3 +149,89 @@ def test_roofline_issue_slots(tmp_path, monkeypatch):
     assert abs(b["bytes_model"]["x_hbm_peak"] - model / 0.5 / 8e12) < 1e-3
     assert b["valu_useful"]["frac"] == out["frac"] and b["valu_issue_slots"]["frac"] == s["frac"]
     assert abs(b["hbm_pmc"]["frac"] - 1e11 / 0.5 / 8e12) < 1e-4 and "binding" in b
+
+
+def test_plain_run_drops_the_side_legs_and_full_keeps_them(monkeypatch):
+    """without --full the counting pass, the side legs and the CPU baselines are off whatever the
+    --no-* flags say; with --full each --no-* flag drops its own leg only"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 2, False, None)
+    assert a.no_count and a.no_post and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-post", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.no_post and not a.no_count and not a.no_cpu_baseline and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame under the size limit is written whole (float32, H x W); a larger one
+    as the same seeded sample of pixels every time, indices beside it, within the limit"""
+    import numpy as np
+    import bench
+    w, h = 40, 30
+    rng = np.random.default_rng(3)
+    rgb = rng.random((w * h, 3), dtype=np.float32)
+    z = rng.random(w * h, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), rgb, z, w, h)
+    got_rgb, got_z = np.load(tmp_path / "whole" / "rgb.npy"), np.load(tmp_path / "whole" / "z.npy")
+    assert got_rgb.dtype == got_z.dtype == np.float32 and got_rgb.shape == (h, w, 3) and got_z.shape == (h, w)
+    assert np.array_equal(got_rgb.reshape(-1, 3), rgb) and np.array_equal(got_z.reshape(-1), z)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["rgb.npy", "z.npy"]
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 24 * 100)
+    idx = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), rgb, z, w, h)
+        files = {f: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)}
+        assert sorted(files) == ["pixel_index.npy", "rgb.npy", "z.npy"]
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+        i = files["pixel_index.npy"].astype(np.int64)
+        assert len(i) == 100 and len(set(i.tolist())) == 100 and (np.diff(i) > 0).all()
+        assert np.array_equal(files["rgb.npy"], rgb[i]) and np.array_equal(files["z.npy"], z[i])
+        idx.append(i)
+    assert np.array_equal(idx[0], idx[1])
+
+
+def test_standin_scene_without_a_writable_tree(tmp_path, monkeypatch):
+    """bench.py's scene when the stand-in mesh is missing and the checkout cannot be written (it
+    belongs to another user): tools/standins.py writes the same mesh and scene to a temporary
+    folder, the Mesh named by absolute path, and the loader reads it whatever the base_dir; where
+    the tree can be written it is used as before and nothing goes elsewhere"""
+    import shutil
+    import rtxpy
+    import standins
+    golden = tmp_path / "golden"
+    (golden / "scenes").mkdir(parents=True)
+    shutil.copy(os.path.join(ROOT, "tests", "golden", "scenes", "scene5.json"), golden / "scenes")
+    monkeypatch.setattr(standins, "GOLDEN", str(golden))
+    monkeypatch.setattr(standins, "_SCRATCH", None)
+    monkeypatch.setitem(standins.STANDINS, "dragon_standin.stl", lambda: standins.dragon_standin(2))  # 320 triangles
+    in_tree = standins.ensure_scene("scene5")
+    assert in_tree == str(golden / "scenes" / "scene5_standin.json") and standins._SCRATCH is None
+    want = rtxpy.Scene.load(in_tree, base_dir=str(golden))
+    mesh = golden / "meshes" / "dragon_standin.stl"
+    mesh_bytes = mesh.read_bytes()
+    mesh.unlink()
+    real_write = standins.write_stl
+
+    def write_stl(path, tris):
+        if path.startswith(str(golden)):
+            raise PermissionError(13, "Permission denied", path)
+        real_write(path, tris)
+
+    monkeypatch.setattr(standins, "write_stl", write_stl)
+    path = standins.ensure_scene("scene5")
+    try:
+        assert os.path.basename(path) == "scene5_standin.json" and not path.startswith(str(golden))
+        assert not mesh.exists() and os.listdir(golden / "meshes") == []
+        with open(path) as fh:
+            entry = [o for o in json.load(fh)["Objects"] if o["type"] == "Mesh"][0]["parameters"]
+        assert os.path.isabs(entry["filename"]) and open(entry["filename"], "rb").read() == mesh_bytes
+        with open(in_tree) as fh:
+            tree_entry = [o for o in json.load(fh)["Objects"] if o["type"] == "Mesh"][0]["parameters"]
+        assert {k: v for k, v in entry.items() if k != "filename"} == {k: v for k, v in tree_entry.items() if k != "filename"}
+        got = rtxpy.Scene.load(path, base_dir=str(golden))
+        assert got.num_objects == want.num_objects == 320 + 3
+    finally:
+        shutil.rmtree(standins._SCRATCH, ignore_errors=True)

@@ -191,7 +191,8 @@ def test_gpu_bench_group_line_on_the_loopback_group(tmp_path):
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(C.ROOT, "bench.py"), "--gpus", "3", "--loopback", "--scene", "scene3",
-           "--width", "192", "--height", "108", "--spp", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--width", "192", "--height", "108", "--spp", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=C.ROOT, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

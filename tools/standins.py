@@ -141,8 +141,9 @@ def ensure_mesh(name, mesh_dir=None):
     return path
 
 
-def standin_scene_json(which):
-    """scene5/scene6 JSON with the Mesh entry pointed at the stand-in."""
+def standin_scene_json(which, mesh_file=None):
+    """scene5/scene6 JSON with the Mesh entry pointed at the stand-in (SURVEY.md §8(d));
+    mesh_file: an absolute path to use instead of the name under meshes/."""
     src = {"scene5": "scene5.json", "scene5_l8": "scene5.json", "scene6": "scene6.json"}[which]
     with open(os.path.join(GOLDEN, "scenes", src)) as fh:
         d = json.load(fh)
@@ -155,19 +156,53 @@ def standin_scene_json(which):
                 p["scale"] = 0.8
             else:
                 p["filename"] = "meshes/menger_standin.stl"
+            if mesh_file:
+                p["filename"] = mesh_file
     return json.dumps(d, indent=1)
 
 
-def ensure_scene(which):
-    """Write tests/golden/scenes/<which>_standin.json and its mesh; return the scene path."""
-    mesh = {"scene5": "dragon_standin.stl", "scene5_l8": "dragon_standin_l8.stl", "scene6": "menger_standin.stl"}[which]
-    ensure_mesh(mesh)
-    path = os.path.join(GOLDEN, "scenes", f"{which}_standin.json")
-    text = standin_scene_json(which)
-    if not os.path.exists(path) or open(path).read() != text:
-        with open(path, "w") as fh:
-            fh.write(text)
+_SCRATCH = None
+
+
+def _scratch_scene(which, mesh):
+    """The same scene and mesh in a temporary folder of this process (removed at exit), the scene's
+    Mesh naming its file by absolute path, which the loader takes as it is whatever the base_dir."""
+    global _SCRATCH
+    if _SCRATCH is None:
+        import atexit
+        import shutil
+        import tempfile
+        _SCRATCH = tempfile.mkdtemp(prefix="rtx_standins_")
+        atexit.register(shutil.rmtree, _SCRATCH, ignore_errors=True)
+    mesh_path = ensure_mesh(mesh, os.path.join(_SCRATCH, "meshes"))
+    os.makedirs(os.path.join(_SCRATCH, "scenes"), exist_ok=True)
+    path = os.path.join(_SCRATCH, "scenes", f"{which}_standin.json")
+    with open(path, "w") as fh:
+        fh.write(standin_scene_json(which, mesh_path))
     return path
+
+
+def ensure_scene(which):
+    """Write tests/golden/scenes/<which>_standin.json and its mesh; return the scene path.
+    __graft_entry__.build() does this for scene5 and scene6, so a built tree is only read here.
+    Where something is missing and the tree cannot be written (another user's checkout, a read-only
+    mount), the scene and mesh go to a temporary folder instead and that scene's path is returned."""
+    mesh = {"scene5": "dragon_standin.stl", "scene5_l8": "dragon_standin_l8.stl", "scene6": "menger_standin.stl"}[which]
+    try:
+        ensure_mesh(mesh)
+        path = os.path.join(GOLDEN, "scenes", f"{which}_standin.json")
+        text = standin_scene_json(which)
+        if not os.path.exists(path) or open(path).read() != text:
+            with open(path, "w") as fh:
+                fh.write(text)
+        return path
+    except PermissionError:
+        return _scratch_scene(which, mesh)
+    except OSError as e:
+        import errno
+        if e.errno != errno.EROFS:
+            raise
+        return _scratch_scene(which, mesh)
 
 
 if __name__ == "__main__":
