@@ -67,6 +67,16 @@ extern "C" hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *i
 extern "C" hipError_t rtx_launch_w8_fill(const DPrim *prims, const DMaterial *mats, const uint32_t *leafmap, uint32_t n, DW8 *out,
 					  hipStream_t stream);
 extern "C" hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes);
+extern "C" size_t rtx_rays_lds_bytes(uint32_t stack_size);
+extern "C" hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu);
+extern "C" hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
+				      uint32_t queues, uint32_t grab, unsigned long long *ctr, uint32_t waves, int count, int any,
+				      hipStream_t stream);
+extern "C" hipError_t rtx_launch_frame_rays(const DFrame *F, float4 *rays, hipStream_t stream);
+extern "C" hipError_t rtx_raysort_temp_bytes(uint32_t n, size_t *bytes);
+extern "C" hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const float lo[3], const float hi[3],
+					 uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp,
+					 size_t temp_bytes, const uint32_t **perm, hipStream_t stream);
 
 /* the code objects of the library's device files (each file's rtx_load_*) */
 extern "C" hipError_t rtx_load_build(void);
@@ -184,6 +194,9 @@ extern "C" void rtx_close(rtx_ctx *c)
 		if (e)
 			(void)hipEventDestroy(e);
 	dfree(c->d_ctr);
+	dfree(c->d_rctr);
+	dfree(c->d_qrays);
+	dfree(c->d_qhits);
 	dfree(c->d_rgb);
 	dfree(c->d_z);
 	if (c->ev0)
@@ -1268,6 +1281,177 @@ extern "C" int rtx_render(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, 
 	return RTX_OK;
 }
 
+/* ------------------------------------------------------------------------ */
+/* ray queries (include/rtx.h rtx_trace_rays*)                              */
+/* ------------------------------------------------------------------------ */
+static hipError_t grow_bytes(void *&ptr, size_t &have, size_t need)
+{
+	if (need <= have)
+		return hipSuccess;
+	if (ptr)
+		(void)hipFree(ptr);
+	ptr = nullptr;
+	have = 0;
+	hipError_t e = hipMalloc(&ptr, need);
+	if (e == hipSuccess)
+		have = need;
+	return e;
+}
+
+static_assert(sizeof(rtx_ray) == 32 && sizeof(rtx_hit) == 32, "k_rays moves a ray / a hit as two float4");
+
+static int rays_check(rtx_ctx *c, uint64_t n, const void *rays, const void *hits, uint32_t flags)
+{
+	if (!c)
+		return fail(RTX_ERR_ARG, "null context");
+	if (flags & ~(uint32_t)(RTX_RAYS_ANY_HIT | RTX_RAYS_REORDER | RTX_RAYS_COUNT))
+		return fail(RTX_ERR_ARG, "unknown ray-query flags 0x%x", flags);
+	if (n > RTX_RAYS_MAX)
+		return fail(RTX_ERR_ARG, "%llu rays above the supported %u per call", (unsigned long long)n, RTX_RAYS_MAX);
+	if (n && (!rays || !hits))
+		return fail(RTX_ERR_ARG, "null ray / hit buffer");
+	if (!c->have_scene)
+		return fail(RTX_ERR_STATE, "rtx_trace_rays before rtx_upload_scene");
+	return RTX_OK;
+}
+
+/* n checked rays on device buffers; touches none of the render's state but grow-only scratch */
+static int rays_common(rtx_ctx *c, uint32_t n, const void *d_rays, void *d_hits, uint32_t flags, hipStream_t stream)
+{
+	rtx_ray_stats rs{};
+	if (!n) {
+		c->ray_stats = rs;
+		return RTX_OK;
+	}
+	if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u)
+		return fail(RTX_ERR_ARG, "ray / hit buffers must be 16-byte aligned");
+	DScene S = c->scene; /* the render sets its own copy's walk and stack fields at every render */
+	S.trace_w8 = (S.w8 && c->opt_trace_walk != RTX_WALK_BVH2) ? 1u : 0u;
+	int per_cu = 0;
+	HIP_TRY(rtx_rays_occupancy(S.stack_size, &per_cu));
+	if (per_cu <= 0)
+		return fail(RTX_ERR_HIP, "ray-query kernel does not fit (LDS %zu B)", rtx_rays_lds_bytes(S.stack_size));
+	const uint32_t packets = (uint32_t)(((uint64_t)n + 63) / 64);
+	const uint32_t waves = (uint32_t)std::min<uint64_t>((uint64_t)per_cu * c->cus, packets);
+	/* the lane-stack entries beyond the LDS part, [entry][grid lane], for THIS grid: the render sizes
+	 * the buffer for its own waves, and a query may come first or run a larger grid */
+	if (S.stack_size > RTX_TRACE_LSTK) {
+		void *p = c->d_ostk;
+		const hipError_t e = grow_bytes(p, c->ostk_bytes, (size_t)waves * 64 * (S.stack_size - RTX_TRACE_LSTK) * sizeof(uint32_t));
+		c->d_ostk = (uint32_t *)p;
+		c->scene.ostk = c->d_ostk;
+		if (e != hipSuccess)
+			return fail(RTX_ERR_NOMEM, "lane-stack overflow buffer: %s", hipGetErrorString(e));
+	}
+	S.ostk = c->d_ostk;
+	if (!c->d_rctr)
+		HIP_TRY(hipMalloc(&c->d_rctr, sizeof(unsigned long long) * RTX_RQ_N));
+	HIP_TRY(hipMemsetAsync(c->d_rctr, 0, sizeof(unsigned long long) * RTX_RQ_N, stream));
+	HIP_TRY(hipEventRecord(c->ev[0], stream));
+	const uint32_t *perm = nullptr;
+	if ((flags & RTX_RAYS_REORDER) && n > 64) { /* one packet has no order to improve */
+		size_t tmp = 0;
+		HIP_TRY(rtx_raysort_temp_bytes(n, &tmp));
+		void *p = c->d_sortbuf;
+		hipError_t e = grow_bytes(p, c->sortbuf_bytes, (size_t)n * 4 * sizeof(uint32_t));
+		c->d_sortbuf = (uint32_t *)p;
+		if (e == hipSuccess)
+			e = grow_bytes(c->d_sorttmp, c->sorttmp_bytes, tmp);
+		if (e != hipSuccess)
+			return fail(RTX_ERR_NOMEM, "ray sort buffers: %s", hipGetErrorString(e));
+		uint32_t *b = c->d_sortbuf;
+		const size_t q = n;
+		HIP_TRY(rtx_launch_raysort((const float4 *)d_rays, n, c->bound_lo, c->bound_hi, b, b + q, b + 2 * q, b + 3 * q,
+					   c->d_sorttmp, c->sorttmp_bytes, &perm, stream));
+	}
+	HIP_TRY(hipEventRecord(c->ev[1], stream));
+	/* one queue per XCD's share of the waves (one counter serves ~80 M grabs a second, which bounds a
+	 * query of any size: 33 M rays took 6.5 ms with one queue, 1.2 ms with eight); packets per grab:
+	 * one, and up to four once a wave has 16 packets or more to take (longer grabs only lengthen the
+	 * tail: 2 M permuted rays 0.37 ms at 1, 0.72 ms at 16) */
+	const uint32_t grab = c->opt_rays_grab ? c->opt_rays_grab : std::max<uint32_t>(1, std::min<uint32_t>(4, packets / (waves * 16)));
+	const uint32_t queues = std::min<uint32_t>(c->opt_rays_queues ? c->opt_rays_queues : RTX_RQ_MAX_QUEUES, waves);
+	HIP_TRY(rtx_launch_rays(&S, (const float4 *)d_rays, (float4 *)d_hits, perm, n, queues, grab, c->d_rctr, waves,
+				(flags & RTX_RAYS_COUNT) != 0, (flags & RTX_RAYS_ANY_HIT) != 0, stream));
+	HIP_TRY(hipEventRecord(c->ev[4], stream));
+	unsigned long long ctr[RTX_RQ_STATS];
+	HIP_TRY(hipMemcpyAsync(ctr, c->d_rctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	float so = 0, k = 0;
+	HIP_TRY(hipEventElapsedTime(&so, c->ev[0], c->ev[1]));
+	HIP_TRY(hipEventElapsedTime(&k, c->ev[1], c->ev[4]));
+	rs.rays = n;
+	rs.hits = ctr[RTX_RQ_HITS];
+	rs.node_visits = ctr[RTX_RQ_NODES];
+	rs.tri_tests = ctr[RTX_RQ_TRIS];
+	rs.sphere_tests = ctr[RTX_RQ_SPHERES];
+	rs.plane_tests = ctr[RTX_RQ_PLANES];
+	rs.far_rays = ctr[RTX_RQ_FAR];
+	rs.kernel_ms = k;
+	rs.sort_ms = perm ? so : 0.0;
+	c->ray_stats = rs;
+	return RTX_OK;
+}
+
+extern "C" int rtx_trace_rays_device(rtx_ctx *c, uint64_t n, const void *d_rays, void *d_hits, uint32_t flags, void *stream)
+{
+	int rc = rays_check(c, n, d_rays, d_hits, flags);
+	if (rc)
+		return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	return rays_common(c, (uint32_t)n, d_rays, d_hits, flags, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int rtx_trace_rays(rtx_ctx *c, uint64_t n, const rtx_ray *rays, rtx_hit *hits, uint32_t flags)
+{
+	int rc = rays_check(c, n, rays, hits, flags);
+	if (rc)
+		return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	if (n) {
+		if (grow_bytes(c->d_qrays, c->qrays_bytes, (size_t)n * sizeof(rtx_ray)) != hipSuccess ||
+		    grow_bytes(c->d_qhits, c->qhits_bytes, (size_t)n * sizeof(rtx_hit)) != hipSuccess)
+			return fail(RTX_ERR_NOMEM, "device copies of %llu rays", (unsigned long long)n);
+		HIP_TRY(hipMemcpyAsync(c->d_qrays, rays, (size_t)n * sizeof(rtx_ray), hipMemcpyHostToDevice, c->stream));
+	}
+	rc = rays_common(c, (uint32_t)n, c->d_qrays, c->d_qhits, flags, c->stream);
+	if (rc)
+		return rc;
+	if (n)
+		HIP_TRY(hipMemcpy(hits, c->d_qhits, (size_t)n * sizeof(rtx_hit), hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
+extern "C" int rtx_frame_rays_device(rtx_ctx *c, const rtx_frame *fr, void *d_rays, void *stream)
+{
+	if (!c || !fr || !d_rays)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (!fr->width || !fr->height || (uint64_t)fr->width * fr->height > RTX_RAYS_MAX)
+		return fail(RTX_ERR_ARG, "bad frame %ux%u", fr->width, fr->height);
+	if ((uintptr_t)d_rays & 15u)
+		return fail(RTX_ERR_ARG, "ray buffer must be 16-byte aligned");
+	HIP_TRY(hipSetDevice(c->device));
+	DFrame F;
+	F.width = fr->width;
+	F.height = fr->height;
+	memcpy(F.corner, fr->corner, 12);
+	memcpy(F.step_x, fr->step_x, 12);
+	memcpy(F.step_y, fr->step_y, 12);
+	memcpy(F.origin, fr->origin, 12);
+	hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+	HIP_TRY(rtx_launch_frame_rays(&F, (float4 *)d_rays, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return RTX_OK;
+}
+
+extern "C" int rtx_get_ray_stats(const rtx_ctx *c, rtx_ray_stats *out)
+{
+	if (!c || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = c->ray_stats;
+	return RTX_OK;
+}
+
 static int post_common(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_post *pp, float *d_rgb, const float *d_z,
 		       hipStream_t stream)
 {
@@ -1393,6 +1577,16 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 		if (value < 0 || value > (1 << 20))
 			return fail(RTX_ERR_ARG, "shade points per tile %lld outside 0..2^20", (long long)value);
 		c->opt_sp_tile = (uint32_t)value;
+		return RTX_OK;
+	case RTX_OPT_RAYS_GRAB:
+		if (value < 0 || value > 64)
+			return fail(RTX_ERR_ARG, "ray-query grab %lld outside 0..64", (long long)value);
+		c->opt_rays_grab = (uint32_t)value;
+		return RTX_OK;
+	case RTX_OPT_RAYS_QUEUES:
+		if (value < 0 || value > RTX_RQ_MAX_QUEUES)
+			return fail(RTX_ERR_ARG, "ray-query queues %lld outside 0..%d", (long long)value, RTX_RQ_MAX_QUEUES);
+		c->opt_rays_queues = (uint32_t)value;
 		return RTX_OK;
 	case RTX_OPT_SHADOW_CULL:
 		if (value < 0 || value > 2)

@@ -331,4 +331,20 @@ enum {
 	RTX_C_N
 };
 
+/* counters of a ray query (k_rays, rtx_trace_rays*): a buffer of its own, reset per query, so the
+ * render's counters above are never touched by one */
+enum {
+	RTX_RQ_HITS = 0, /* rays that hit */
+	RTX_RQ_NODES,    /* RTX_RAYS_COUNT: traversal counts, as RTX_C_NODES .. RTX_C_FARC */
+	RTX_RQ_TRIS,
+	RTX_RQ_SPHERES,
+	RTX_RQ_PLANES,
+	RTX_RQ_FAR,
+	RTX_RQ_STATS,                 /* the counters above are read back */
+	RTX_RQ_HEADS = 16,            /* k_rays' packet queue heads, one per queue, each on a 128-byte line of its own */
+	RTX_RQ_HEAD_STRIDE = 16,
+	RTX_RQ_MAX_QUEUES = 8,        /* one per XCD's share of the workgroups (dealt round-robin over the XCDs) */
+	RTX_RQ_N = RTX_RQ_HEADS + RTX_RQ_MAX_QUEUES * RTX_RQ_HEAD_STRIDE
+};
+
 #endif

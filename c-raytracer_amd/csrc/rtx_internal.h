@@ -120,6 +120,11 @@ struct rtx_ctx {
 	float *d_rgb = nullptr, *d_z = nullptr;
 	size_t fb_pixels = 0;
 	rtx_stats stats{};
+	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
+	unsigned long long *d_rctr = nullptr;
+	void *d_qrays = nullptr, *d_qhits = nullptr;
+	size_t qrays_bytes = 0, qhits_bytes = 0;
+	rtx_ray_stats ray_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;
@@ -131,6 +136,8 @@ struct rtx_ctx {
 	int opt_frame = RTX_FRAME_AUTO;
 	uint32_t opt_chunk = 0;   /* most tiles per chunk (0: as many as the shade-point budget allows) */
 	uint32_t opt_sp_tile = 0; /* shade points per tile a chunk is sized for (0: the estimate / last render's count) */
+	uint32_t opt_rays_grab = 0;   /* RTX_OPT_RAYS_GRAB: packets per k_rays queue grab (0: automatic) */
+	uint32_t opt_rays_queues = 0; /* RTX_OPT_RAYS_QUEUES: k_rays packet queues (0: automatic) */
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
 	uint32_t mem_share = 1;   /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */

@@ -75,6 +75,64 @@ extern "C" hipError_t rtx_launch_spsort(const float4 *sp, uint32_t n, const floa
 	return e;
 }
 
+/*
+ * Ray-batch ordering for k_rays (RTX_RAYS_REORDER): a caller's rays sorted by where they start and
+ * which way they point, so a packet's 64 lanes walk one part of the tree.  Key: the 27-bit Morton
+ * code of the origin in the bounded objects' box (9 bits per axis, clamped: origins outside it
+ * land on its faces) in the high bits, the direction's octant (bit a: dir[a] >= 0) in the low 3.
+ * As above, order changes which lane traces a ray, never its result: k_rays reads ray perm[i] and
+ * writes hit perm[i].
+ */
+#define RTX_RAYKEY_BITS 30
+
+__global__ __launch_bounds__(256) void k_raykey(const float4 *__restrict__ rays, uint32_t n, float lox, float loy,
+						 float loz, float sx, float sy, float sz, uint32_t *__restrict__ keys,
+						 uint32_t *__restrict__ vals)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (j >= n)
+		return;
+	const float4 o = rays[2 * j], d = rays[2 * j + 1];
+	/* NaN coordinates land in cell 0 (fmaxf / fminf return the other operand) */
+	const float x = fminf(fmaxf((o.x - lox) * sx, 0.f), 511.f);
+	const float y = fminf(fmaxf((o.y - loy) * sy, 0.f), 511.f);
+	const float z = fminf(fmaxf((o.z - loz) * sz, 0.f), 511.f);
+	const uint32_t m = spread10((uint32_t)x) | (spread10((uint32_t)y) << 1) | (spread10((uint32_t)z) << 2);
+	const uint32_t oct = (d.x >= 0.f ? 1u : 0u) | (d.y >= 0.f ? 2u : 0u) | (d.z >= 0.f ? 4u : 0u);
+	keys[j] = (m << 3) | oct;
+	vals[j] = (uint32_t)j;
+}
+
+extern "C" hipError_t rtx_raysort_temp_bytes(uint32_t n, size_t *bytes)
+{
+	hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
+	return hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, k, v, (int)n, 0, RTX_RAYKEY_BITS);
+}
+
+/* rays: n rtx_ray records; keys / vals: two buffers of n each; *perm <- the sorted ray indices */
+extern "C" hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const float lo[3], const float hi[3],
+					 uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp,
+					 size_t temp_bytes, const uint32_t **perm, hipStream_t stream)
+{
+	*perm = vals0;
+	if (!n)
+		return hipSuccess;
+	float s[3];
+	for (int a = 0; a < 3; a++) {
+		const float ext = hi[a] - lo[a];
+		s[a] = ext > 0.f ? 512.f / ext : 0.f;
+	}
+	hipLaunchKernelGGL(k_raykey, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, rays, n, lo[0], lo[1],
+			   lo[2], s[0], s[1], s[2], keys0, vals0);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess)
+		return e;
+	hipcub::DoubleBuffer<uint32_t> k(keys0, keys1), v(vals0, vals1);
+	e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k, v, (int)n, 0, RTX_RAYKEY_BITS, stream);
+	*perm = v.Current();
+	return e;
+}
+
 /* the code object of this file on the current device, loaded now (rtx_open) rather than at the
  * first launch inside an upload or a render */
 extern "C" __attribute__((visibility("hidden"))) hipError_t rtx_load_sort(void)

@@ -16,6 +16,9 @@
  *           contiguous array at tile end.
  *  k_accum  (one wave per tile) adds the shade points' light terms, computed by
  *           k_shadow, to their pixels in emission order.
+ *  k_rays   (persistent, one wave per workgroup; 64-ray packets from device queues) the
+ *           closest or any hit of a caller's ray batch (rtx_trace_rays*), with k_trace's
+ *           walks and hit records; k_frame_rays writes a frame's primary rays for it.
  *  k_kat    per-function known answers of the device intersectors/samplers.
  *
  * No float atomics anywhere: a pixel's value is bit-identical whichever wave,
@@ -37,11 +40,14 @@ struct TraceCount {
 	uint32_t nodes, tris, sph, pln, far;
 };
 
-template <bool COUNT>
+/* ANY / LIM (the ray queries, k_rays): LIM takes the caller's t_out as the ray's upper bound (hits
+ * need t < it) where the renderer's rays start from FLT_MAX; ANY ends the lane's walk, and the plane
+ * and emitter loops, at the first hit accepted under that bound.  Both false: the renderer's code. */
+template <bool COUNT, bool ANY = false, bool LIM = false>
 __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 o, f3 d, uint32_t inside, float &t_out,
 				   uint32_t &hid_out, TraceCount &tc)
 {
-	float tbest = FLT_MAX;
+	float tbest = LIM ? t_out : FLT_MAX;
 	uint32_t hid = RTX_NONE;
 	if (act && isnan3(d)) /* TIR / degenerate directions hit nothing */
 		act = false;
@@ -74,6 +80,10 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 			if (hit_plane(ld3(pl.n), pl.d, o, d, pl.eps, t) && t < tbest) {
 				tbest = t;
 				hid = RTX_PLANE_BIT | i;
+				if (ANY) {
+					act = false;
+					break;
+				}
 			}
 		}
 	}
@@ -132,8 +142,12 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 					if (h && t < tbest) {
 						tbest = t;
 						hid = first + k;
+						if (ANY)
+							break;
 					}
 				}
+				if (ANY && hid != RTX_NONE) /* a plane hit never enters the walk: this hit is the walk's */
+					break;
 				if (sp == 0)
 					break;
 				ref = pop();
@@ -191,7 +205,7 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 /* FAR: some lane of the wave has a far origin (t0 and the per-lane far flag live across the walk);
  * the other instances take t0 = 0 and no far lane as constants, so the waves of near rays (all of
  * them in the reference scenes' views) keep those registers for the walk */
-template <bool COUNT, int OCT, bool FAR>
+template <bool COUNT, int OCT, bool FAR, bool ANY = false>
 __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uint32_t *ostk, size_t ostride, f3 o, f3 d,
 					      f3 ob, f3 inv, float t0_, bool far_, float &tbest, uint32_t &hid,
 					      TraceCount &tc)
@@ -279,6 +293,8 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 			if (h && t < tbest) {
 				tbest = t;
 				hid = __float_as_uint(ldg4(pr, 48).w);
+				if (ANY)
+					return;
 			}
 		}
 		if (RTX_TRACE_CULL && tin > tbest) /* every hit inner child starts beyond the closest hit */
@@ -312,11 +328,11 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 	}
 }
 
-template <bool COUNT>
+template <bool COUNT, bool ANY = false, bool LIM = false>
 __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o, f3 d, uint32_t inside, float &t_out,
 				 uint32_t &hid_out, TraceCount &tc)
 {
-	float tbest = FLT_MAX;
+	float tbest = LIM ? t_out : FLT_MAX;
 	uint32_t hid = RTX_NONE;
 	if (act && isnan3(d)) /* TIR / degenerate directions hit nothing */
 		act = false;
@@ -349,6 +365,10 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 			if (hit_plane(ld3(pl.n), pl.d, o, d, pl.eps, t) && t < tbest) {
 				tbest = t;
 				hid = RTX_PLANE_BIT | i;
+				if (ANY) {
+					act = false;
+					break;
+				}
 			}
 		}
 	}
@@ -381,6 +401,10 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 				if (h && t < tbest) {
 					tbest = t;
 					hid = e.prim;
+					if (ANY) {
+						act = false;
+						break;
+					}
 				}
 			}
 		}
@@ -393,18 +417,18 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 		const uint32_t sel = ballot(act & (oct != lead)) ? 8u : lead;
 		const bool anyfar = ballot(far) != 0;
 		if (act && anyfar) {
-			closest_walk8<COUNT, 8, true>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
+			closest_walk8<COUNT, 8, true, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
 		} else if (act) {
 			switch (sel) {
 #define RTX_CWALK(K)                                                                           \
 	case K:                                                                                    \
-		closest_walk8<COUNT, K, false>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc); \
+		closest_walk8<COUNT, K, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc); \
 		break;
 				RTX_CWALK(0) RTX_CWALK(1) RTX_CWALK(2) RTX_CWALK(3) RTX_CWALK(4) RTX_CWALK(5) RTX_CWALK(6)
 				RTX_CWALK(7)
 #undef RTX_CWALK
 			default:
-				closest_walk8<COUNT, 8, false>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
+				closest_walk8<COUNT, 8, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
 				break;
 			}
 		}
@@ -414,14 +438,14 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 }
 
 /* the closest-hit walk of this scene: the 8-wide tree when built and chosen (DScene.trace_w8) */
-template <bool COUNT>
+template <bool COUNT, bool ANY = false, bool LIM = false>
 __device__ __forceinline__ void trace_closest(const DScene &S, uint32_t *stk, bool act, f3 o, f3 d, uint32_t inside,
 					      float &t_out, uint32_t &hid_out, TraceCount &tc)
 {
 	if (S.trace_w8)
-		trace_closest_w8<COUNT>(S, stk, act, o, d, inside, t_out, hid_out, tc);
+		trace_closest_w8<COUNT, ANY, LIM>(S, stk, act, o, d, inside, t_out, hid_out, tc);
 	else
-		trace_closest_bvh2<COUNT>(S, stk, act, o, d, inside, t_out, hid_out, tc);
+		trace_closest_bvh2<COUNT, ANY, LIM>(S, stk, act, o, d, inside, t_out, hid_out, tc);
 }
 
 struct HitInfo {
@@ -535,6 +559,18 @@ __device__ __forceinline__ void spr_store(float4 *rec, const ShadePt &s)
 /* ------------------------------------------------------------------------ */
 /* k_trace: per 8x8 tile, every cast_ray() of the tile's ray trees          */
 /* ------------------------------------------------------------------------ */
+/* direction d of pixel (px, py)'s primary ray from o (render.c:353-363): P = corner + row*vy, then
+ * += vx (col+1) times, sequentially.  One text for k_trace and k_frame_rays, so both form one ray
+ * bit for bit (a macro: as a function it changed k_trace's register allocation) */
+#define RTX_PRIMARY_DIR(F, px, py, o, d)                                                     \
+	do {                                                                                 \
+		f3 pp = add3(mul3s(ld3((F).step_y), (float)(py)), ld3((F).corner));          \
+		const f3 sx = ld3((F).step_x);                                               \
+		for (uint32_t c = 0; c <= (px); c++)                                         \
+			pp = add3(pp, sx);                                                   \
+		(d) = norm3(sub3(pp, (o)));                                                  \
+	} while (0)
+
 struct TraceOut {
 	float4 *staging; /* this wave's staging region */
 	uint32_t cap;    /* records */
@@ -666,11 +702,7 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 		uint64_t key = 0;
 		bool primary = true;
 		if (act) {
-			f3 pp = add3(mul3s(ld3(F.step_y), (float)py), ld3(F.corner));
-			const f3 sx = ld3(F.step_x);
-			for (uint32_t c = 0; c <= px; c++)
-				pp = add3(pp, sx);
-			d = norm3(sub3(pp, o));
+			RTX_PRIMARY_DIR(F, px, py, o, d);
 			key = rtx_key_pixel(P.seed, py * F.width + px);
 		}
 		uint32_t top = 0;
@@ -891,6 +923,109 @@ __global__ __launch_bounds__(WAVE) void k_accum(DFrame F, DParams P, const uint2
 	}
 }
 
+/* ------------------------------------------------------------------------ */
+/* k_rays: closest / any hit of a caller's ray batch (rtx_trace_rays*)      */
+/* ------------------------------------------------------------------------ */
+/* Persistent waves, one per workgroup like k_trace (the closest walk's lane stack is per
+ * workgroup: LDS, then DScene.ostk by blockIdx.x / gridDim.x, which the host sizes for THIS
+ * grid), taking 64-ray packets from atomic counters, `grab` consecutive packets at a time.  A
+ * walk of a packet is short next to a tile's ray trees, and one counter serves about 80 M
+ * device-wide atomics a second (33 M rays took 6.5 ms whatever they hit; 1.2 ms with eight), so the packets are dealt
+ * over `queues` counters on lines of their own: wave b takes from queue b % queues, which owns the
+ * grabs j = queue + k * queues (an equal share, interleaved, for an equal share of the waves).  A ray is two float4 (rtx_ray: origin, tmax |
+ * dir, pad), a hit two float4 (rtx_hit: t, object, material, outside | n, pad).  With perm (the
+ * RTX_RAYS_REORDER sort's index list) lane i of a packet traces ray perm[i] and writes hit
+ * perm[i]: a ray's result never depends on the rays it shares a wave with, as the closest t is
+ * a minimum over accepted hits and the box tests only cull. */
+template <bool COUNT, bool ANY>
+__global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_rays(DScene S, const float4 *__restrict__ rays,
+							      float4 *__restrict__ hits, const uint32_t *__restrict__ perm,
+							      uint32_t n, uint32_t queues, uint32_t grab,
+							      unsigned long long *__restrict__ ctr)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+	uint32_t *stk = (uint32_t *)lds_raw;
+	const uint32_t packets = (uint32_t)(((uint64_t)n + WAVE - 1) / WAVE);
+	TraceCount tc = { 0, 0, 0, 0, 0 };
+	u64 n_hits = 0;
+	const uint32_t queue = blockIdx.x % queues;
+	unsigned long long *head = ctr + RTX_RQ_HEADS + (size_t)queue * RTX_RQ_HEAD_STRIDE;
+	uint64_t pk = 0, pk_end = 0;
+	for (;;) {
+		if (pk == pk_end) {
+			uint32_t k = 0;
+			if (lane_id() == 0)
+				k = (uint32_t)atomicAdd(head, 1ull);
+			k = uni(__shfl(k, 0, WAVE));
+			pk = ((uint64_t)k * queues + queue) * grab;
+			if (pk >= packets)
+				break;
+			pk_end = pk + grab < packets ? pk + grab : packets;
+		}
+		const uint64_t i = pk++ * WAVE + lane_id();
+		const bool act = i < n;
+		size_t idx = 0;
+		float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, 0.f);
+		if (act) {
+			idx = perm ? (size_t)perm[i] : (size_t)i;
+			r0 = rays[2 * idx];
+			r1 = rays[2 * idx + 1];
+		}
+		const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
+		float t = r0.w < FLT_MAX ? r0.w : FLT_MAX; /* tmax: INFINITY (or NaN) = the renderer's unbounded ray */
+		uint32_t hid;
+		lds_sync();
+		trace_closest<COUNT, ANY, true>(S, stk, act, o, d, RTX_NONE, t, hid, tc);
+		const bool hit = act && hid != RTX_NONE;
+		float4 h0 = make_float4(0.f, __uint_as_float(0xFFFFFFFFu), __uint_as_float(0xFFFFFFFFu), 0.f);
+		float4 h1 = make_float4(0.f, 0.f, 0.f, 0.f);
+		if (hit) {
+			const HitInfo h = hit_info(S, hid, o, d, t);
+			h0 = make_float4(t, __uint_as_float(h.obj), __uint_as_float(h.mat), __uint_as_float(h.outside ? 1u : 0u));
+			h1 = make_float4(h.n.x, h.n.y, h.n.z, 0.f);
+		}
+		if (act) {
+			hits[2 * idx] = h0;
+			hits[2 * idx + 1] = h1;
+		}
+		n_hits += popc64(ballot(hit));
+	}
+	if (COUNT) {
+		u64 a = tc.nodes, b = tc.tris, c = tc.sph, d2 = tc.pln, f = tc.far;
+#pragma unroll
+		for (int o2 = 32; o2 > 0; o2 >>= 1) {
+			a += __shfl_xor(a, o2, WAVE);
+			b += __shfl_xor(b, o2, WAVE);
+			c += __shfl_xor(c, o2, WAVE);
+			d2 += __shfl_xor(d2, o2, WAVE);
+			f += __shfl_xor(f, o2, WAVE);
+		}
+		if (lane_id() == 0) {
+			atomicAdd(&ctr[RTX_RQ_NODES], a);
+			atomicAdd(&ctr[RTX_RQ_TRIS], b);
+			atomicAdd(&ctr[RTX_RQ_SPHERES], c);
+			atomicAdd(&ctr[RTX_RQ_PLANES], d2);
+			atomicAdd(&ctr[RTX_RQ_FAR], f);
+		}
+	}
+	if (lane_id() == 0 && n_hits)
+		atomicAdd(&ctr[RTX_RQ_HITS], n_hits);
+}
+
+/* the W*H primary rays of a frame as rtx_ray records, row-major, tmax = INFINITY: k_trace's own rays */
+__global__ __launch_bounds__(256) void k_frame_rays(DFrame F, float4 *__restrict__ rays)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= (uint64_t)F.width * F.height)
+		return;
+	const uint32_t px = (uint32_t)(i % F.width), py = (uint32_t)(i / F.width);
+	const f3 o = ld3(F.origin);
+	f3 d;
+	RTX_PRIMARY_DIR(F, px, py, o, d);
+	rays[2 * i] = make_float4(o.x, o.y, o.z, INFINITY);
+	rays[2 * i + 1] = make_float4(d.x, d.y, d.z, 0.f);
+}
+
 __global__ void k_kat(int kind, uint32_t n, const float *__restrict__ in, float *__restrict__ out, int u32mode)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1068,6 +1203,46 @@ extern "C" hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const 
 	if (!ntiles || !rgb)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_accum, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb);
+	return hipGetLastError();
+}
+
+/* k_rays keeps only the closest walk's LDS lane-stack entries */
+extern "C" size_t rtx_rays_lds_bytes(uint32_t stack_size)
+{
+	const size_t lstk = stack_size < RTX_TRACE_LSTK ? stack_size : RTX_TRACE_LSTK;
+	return lstk * WAVE * 4;
+}
+
+extern "C" hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu)
+{
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_rays<false, false>, WAVE,
+							     rtx_rays_lds_bytes(stack_size));
+}
+
+/* S->ostk must hold waves * 64 * (stack_size - RTX_TRACE_LSTK) entries: this launch's own grid */
+extern "C" hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
+				      uint32_t queues, uint32_t grab, unsigned long long *ctr, uint32_t waves, int count, int any,
+				      hipStream_t stream)
+{
+	const size_t lds = rtx_rays_lds_bytes(S->stack_size);
+#define RTX_RAYS_LAUNCH(C, A) \
+	hipLaunchKernelGGL((k_rays<C, A>), dim3(waves), dim3(WAVE), lds, stream, *S, rays, hits, perm, n, queues, grab, ctr)
+	if (count && any)
+		RTX_RAYS_LAUNCH(true, true);
+	else if (count)
+		RTX_RAYS_LAUNCH(true, false);
+	else if (any)
+		RTX_RAYS_LAUNCH(false, true);
+	else
+		RTX_RAYS_LAUNCH(false, false);
+#undef RTX_RAYS_LAUNCH
+	return hipGetLastError();
+}
+
+extern "C" hipError_t rtx_launch_frame_rays(const DFrame *F, float4 *rays, hipStream_t stream)
+{
+	const uint64_t n = (uint64_t)F->width * F->height;
+	hipLaunchKernelGGL(k_frame_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, *F, rays);
 	return hipGetLastError();
 }
 

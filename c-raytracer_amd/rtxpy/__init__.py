@@ -268,6 +268,42 @@ class Renderer:
         _check(self.lib.rtx_get_stats(self._ctx, C.byref(s)))
         return s
 
+    def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
+        """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
+        Returns a dict of numpy arrays: t (n,) float32 (0 on a miss), object / material (n,) int32
+        (-1 on a miss), outside (n,) uint32, n (n, 3) float32."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        if origins.shape != dirs.shape:
+            raise ValueError("origins and dirs differ in shape")
+        n = origins.shape[0]
+        rays = np.zeros(n, abi.RAY_DTYPE)
+        rays["origin"] = origins
+        rays["dir"] = dirs
+        rays["tmax"] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+        hits = np.zeros(n, abi.HIT_DTYPE)
+        flags = ((abi.RTX_RAYS_ANY_HIT if any_hit else 0) | (abi.RTX_RAYS_REORDER if reorder else 0)
+                 | (abi.RTX_RAYS_COUNT if count else 0))
+        _check(self.lib.rtx_trace_rays(self._ctx, n, rays.ctypes.data if n else None, hits.ctypes.data if n else None,
+                                       flags))
+        return {k: hits[k].copy() for k in ("t", "object", "material", "outside", "n")}
+
+    def trace_rays_device(self, n, d_rays, d_hits, flags=0, stream=None):
+        """rtx_trace_rays_device: d_rays / d_hits are device pointers (ints, e.g. a torch tensor's
+        data_ptr()) to n rtx_ray / rtx_hit records (8 float32 words each); stream: hipStream_t as int or None."""
+        _check(self.lib.rtx_trace_rays_device(self._ctx, n, C.c_void_p(d_rays), C.c_void_p(d_hits), flags,
+                                              C.c_void_p(stream) if stream else None))
+
+    def frame_rays_device(self, frame, d_rays, stream=None):
+        """rtx_frame_rays_device: the frame's width * height primary rays into the device buffer d_rays"""
+        _check(self.lib.rtx_frame_rays_device(self._ctx, C.byref(frame), C.c_void_p(d_rays),
+                                              C.c_void_p(stream) if stream else None))
+
+    def ray_stats(self):
+        s = abi.RayStats()
+        _check(self.lib.rtx_get_ray_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)

@@ -94,7 +94,7 @@ RTX_SHADOW_LINEAR_MAX = 8
 RTX_FRAME_AUTO, RTX_FRAME_WORLD = 0, 1
 RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_OPT_SHADOW_GRAB, \
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
-    RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+    RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 
@@ -106,6 +106,30 @@ class Post(C.Structure):
                 ("mist_start", C.c_float), ("mist_depth", C.c_float), ("mist_falloff", C.c_int32),
                 ("mist_color", F3)]
 
+
+# ray queries (rtx_trace_rays*)
+RTX_RAYS_ANY_HIT, RTX_RAYS_REORDER, RTX_RAYS_COUNT = 1, 2, 4
+RTX_RAYS_MAX = 0x7FFFFFFF
+
+
+class Ray(C.Structure):
+    _fields_ = [("origin", F3), ("tmax", C.c_float), ("dir", F3), ("pad_", C.c_uint32)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("object", C.c_int32), ("material", C.c_int32), ("outside", C.c_uint32),
+                ("n", F3), ("pad_", C.c_uint32)]
+
+
+class RayStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64),
+                ("sphere_tests", C.c_uint64), ("plane_tests", C.c_uint64), ("far_rays", C.c_uint64),
+                ("kernel_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
+# numpy views of rtx_ray / rtx_hit arrays (the same 32-byte layouts)
+RAY_DTYPE = [("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("pad_", "<u4")]
+HIT_DTYPE = [("t", "<f4"), ("object", "<i4"), ("material", "<i4"), ("outside", "<u4"), ("n", "<f4", 3), ("pad_", "<u4")]
 
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
@@ -122,7 +146,8 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree",
                "rtx_group_set_builder", "rtx_group_set_option", "rtx_group_upload_scene", "rtx_group_render", "rtx_group_get_stats", "rtx_group_device_stats",
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
-               "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame"]
+               "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
+               "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -236,6 +261,14 @@ def declare_rtx(lib):
     lib.rtx_tree_frame.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_double)]
     lib.rtx_tree_frame.restype = C.c_int
+    lib.rtx_trace_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.rtx_trace_rays.restype = C.c_int
+    lib.rtx_trace_rays_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.rtx_trace_rays_device.restype = C.c_int
+    lib.rtx_frame_rays_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_void_p]
+    lib.rtx_frame_rays_device.restype = C.c_int
+    lib.rtx_get_ray_stats.argtypes = [C.c_void_p, C.POINTER(RayStats)]
+    lib.rtx_get_ray_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

@@ -300,12 +300,16 @@ enum rtx_option {
 	RTX_OPT_SP_PER_TILE = 10,     /* shade points per tile a chunk is sized for (0 = automatic, default): a
 	                               * chunk that overflows is halved and retried, so any value gives the same
 	                               * image (tests drive the overflow path with a low one) */
-	RTX_OPT_SHADOW_CULL = 11      /* 1 (default): a packet of one shade point's light samples skips the 8-wide
+	RTX_OPT_SHADOW_CULL = 11,     /* 1 (default): a packet of one shade point's light samples skips the 8-wide
 	                               * walk when the cone from the point around the light's bounding sphere
 	                               * meets no box of the tree's top two levels (the walk would find nothing,
 	                               * so the image is the same); 2: packets of several points (points with
 	                               * fewer than 64 samples) too, when every lane's point is clear for its
 	                               * emitter (emitters 0..7); 0: every packet walks */
+	RTX_OPT_RAYS_GRAB = 12,       /* ray queries: 64-ray packets a wave takes per queue grab, 1..64 (0 = automatic,
+	                               * default: 1, up to 4 for batches of 16 packets per wave and more) */
+	RTX_OPT_RAYS_QUEUES = 13      /* ray queries: atomic packet queues the waves are dealt over, 1..8 (0 =
+	                               * automatic, default: 8); any value gives the same hits */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -319,6 +323,62 @@ const char *rtx_last_error(void);
  * host memory, at most `capacity` of them; *count = the tree's entry count (0: no 8-wide tree),
  * frame[6] = its 16-bit frame (origin, scale per axis).  entries may be NULL to query the count. */
 int rtx_read_wide_tree(rtx_ctx *ctx, void *entries, uint32_t capacity, uint32_t *count, float frame[6]);
+
+/*
+ * Ray queries: the closest hit (or any hit) of a caller's own rays against the uploaded scene,
+ * what the reference's get_closest_intersection (render.c:118-124) finds with inside_object ==
+ * NULL: every plane (unbound_objects[]), the emitters the 8-wide tree leaves out and the tree
+ * (RTX_OPT_TRACE_WALK: the 8-wide tree or the float BVH2), each object with its own epsilon as
+ * the lower bound of t (object.c:254-265, 356-365, 473-488), the exact intersectors of the
+ * renderer.  A query renders nothing and leaves rtx_get_stats, the next render's image and its
+ * chunk sizing as they were; it shares (and may grow) the context's scratch buffers, so like
+ * every call on a context it must not run concurrently with another.
+ */
+typedef struct rtx_ray {          /* 32 B */
+	float origin[3];
+	float tmax;               /* hits need t < tmax; INFINITY (or NaN) = unbounded, as the renderer's rays */
+	float dir[3];             /* unit length (the caller's duty: t is in units of |dir|); a NaN component =
+	                           * miss, as cast_ray's total-internal-reflection rays */
+	uint32_t pad_;
+} rtx_ray;
+typedef struct rtx_hit {          /* 32 B */
+	float t;                  /* hit distance; 0 on a miss (as the z buffer, render.c:304-305) */
+	int32_t object;           /* index into rtx_scene_desc.objects; -1 on a miss */
+	int32_t material;         /* index into rtx_scene_desc.materials; -1 on a miss */
+	uint32_t outside;         /* signbit(n . dir) (render.c:166-167); 0 on a miss */
+	float n[3];               /* the normal cast_ray shades with: sphere (P - centre) / r, the triangle's n,
+	                           * a plane's n turned to face the ray (object.c:254-265, 356-365, 473-488) */
+	uint32_t pad_;
+} rtx_hit;
+enum {
+	RTX_RAYS_ANY_HIT = 1, /* stop at the first hit found with t < tmax (an occlusion test): whether a ray
+	                       * hits is exact, but t / object / n are that hit's, not the closest one's */
+	RTX_RAYS_REORDER = 2, /* sort the batch for coherence first (key: Morton code of the origin in the
+	                       * bounded objects' box, then the direction's octant); results land in input order */
+	RTX_RAYS_COUNT = 4    /* fill the traversal counters of rtx_ray_stats (slower kernel instance) */
+};
+#define RTX_RAYS_MAX 0x7FFFFFFFu /* most rays per call (2^31 - 1) */
+/* n rays from / hits to HOST buffers.  n == 0 returns RTX_OK and launches nothing; RTX_ERR_STATE
+ * before an upload; RTX_ERR_ARG for a null buffer with n > 0, unknown flag bits or n > RTX_RAYS_MAX.
+ * A ray's t never depends on the batch it is in, its order or RTX_RAYS_REORDER (the closest t is
+ * a minimum over the accepted hits; box tests only cull); object may differ between two orders
+ * only where two objects' intersectors return the very same t (the first one found keeps it). */
+int rtx_trace_rays(rtx_ctx *ctx, uint64_t n, const rtx_ray *rays, rtx_hit *hits, uint32_t flags);
+/* Same on DEVICE buffers of the context's device (16-byte aligned), enqueued on `stream`
+ * (hipStream_t, NULL = the context's own); synchronises the stream.  hits[n..] is not written. */
+int rtx_trace_rays_device(rtx_ctx *ctx, uint64_t n, const void *d_rays, void *d_hits, uint32_t flags, void *stream);
+/* The width * height primary rays of a frame into a DEVICE buffer, row-major (row 0 = top), tmax =
+ * INFINITY: the rays rtx_render traces for it (render.c:353-363), formed by the same device code,
+ * so a closest query of them returns the render's z buffer bit for bit (max_bounces >= 1). */
+int rtx_frame_rays_device(rtx_ctx *ctx, const rtx_frame *frame, void *d_rays, void *stream);
+typedef struct rtx_ray_stats {    /* the last rtx_trace_rays* of the context */
+	uint64_t rays, hits;
+	/* only with RTX_RAYS_COUNT (as rtx_stats' closest-hit counters) */
+	uint64_t node_visits, tri_tests, sphere_tests, plane_tests, far_rays;
+	double kernel_ms;         /* k_rays, HIP events */
+	double sort_ms;           /* RTX_RAYS_REORDER: key kernel + radix sort (else 0) */
+} rtx_ray_stats;
+int rtx_get_ray_stats(const rtx_ctx *ctx, rtx_ray_stats *out);
 
 /*
  * Several devices rendering one frame (the reference's own parallel point is
