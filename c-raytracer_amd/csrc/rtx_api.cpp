@@ -159,6 +159,7 @@ static void free_scene(rtx_ctx *c)
 	dfree(c->d_emitters);
 	dfree(c->d_lin);
 	dfree(c->d_cull);
+	dfree(c->d_lsph);
 	dfree(c->d_qnodes);
 	dfree(c->d_top);
 	dfree(c->d_w8);
@@ -835,6 +836,27 @@ static int build_cull(rtx_ctx *c, const HostScene &hs, uint32_t num_w8, uint32_t
 	return RTX_OK;
 }
 
+/* k_shadow's per-point masks (DScene.lsph, RTX_OPT_SHADOW_POINT): the bounding spheres of the
+ * records k_shadow tests one by one, in their order (the emitters an 8-wide tree leaves out, or a
+ * tiny scene's objects).  More than RTX_CULL_MAX: none (their tests then always run). */
+static int build_lsph(rtx_ctx *c, const std::vector<DEmitter> &recs, uint32_t *n_out)
+{
+	*n_out = 0;
+	if (recs.empty() || recs.size() > RTX_CULL_MAX)
+		return RTX_OK;
+	std::vector<float4> sph(recs.size());
+	for (size_t k = 0; k < recs.size(); k++) {
+		float s[4];
+		rtx_record_sphere(recs[k].type == RTX_SPHERE, recs[k].p0, recs[k].p1, recs[k].p2, recs[k].radius, s);
+		sph[k] = make_float4(s[0], s[1], s[2], s[3]);
+	}
+	int rc = upload(c->d_lsph, sph, c->stream);
+	if (rc)
+		return rc;
+	*n_out = (uint32_t)sph.size();
+	return RTX_OK;
+}
+
 int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 {
 	int rc;
@@ -901,6 +923,10 @@ int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 	uint32_t ncull = 0; /* the cone cull needs the emitters out of the tree (else a light's own leaf meets every cone) */
 	if (have_w8 && hs.w8noemit && hs.lin.empty() && (rc = build_cull(c, hs, num_w8, &ncull)))
 		return rc;
+	uint32_t nlsph = 0; /* the records rtx_launch_shadow lists: the emitters out of the 8-wide tree, else `lin` */
+	static const std::vector<DEmitter> none;
+	if ((rc = build_lsph(c, have_w8 ? (hs.w8noemit ? hs.emit : none) : hs.lin, &nlsph)))
+		return rc;
 	memcpy(c->bound_lo, hs.bound_lo, 12);
 	memcpy(c->bound_hi, hs.bound_hi, 12);
 	DScene &S = c->scene;
@@ -936,6 +962,8 @@ int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 	S.tf = hs.tf;
 	S.cull = ncull ? (const float *)c->d_cull : nullptr;
 	S.num_cull = ncull;
+	S.lsph = nlsph ? (const float *)c->d_lsph : nullptr;
+	S.num_lsph = nlsph;
 	c->total_lights = 0;
 	for (const DEmitter &e : hs.emit)
 		c->total_lights += e.num_lights;
@@ -1176,6 +1204,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		if (!c->opt_cull)
 			Ssh.num_cull = 0;
 		Ssh.cull_slots = c->opt_cull == 2 ? 1u : 0u;
+		Ssh.point = (c->opt_cull && c->opt_point) ? 1u : 0u; /* RTX_OPT_SHADOW_POINT */
 		HIP_TRY(rtx_launch_shadow(&Ssh, &P, c->d_sp, perm, n_sp, per_wave, slot_b, c->d_contrib, c->d_ctr,
 					  p->count_traversal, (uint32_t)c->cus, stream));
 		HIP_TRY(hipEventRecord(c->ev[2], stream));
@@ -1227,6 +1256,9 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	st.far_shadow_rays = ctr[RTX_C_FARS];
 	st.shadow_stack_spills = ctr[RTX_C_SSPILL];
 	st.shadow_cone_clear = ctr[RTX_C_SCLEAR];
+	c->pstats.shadow_plane_skipped = ctr[RTX_C_SPSKIP];
+	c->pstats.shadow_lin_skipped = ctr[RTX_C_SLSKIP];
+	c->pstats.shadow_point_clear = ctr[RTX_C_SPCLEAR];
 	st.node_visits = ctr[RTX_C_NODES] + st.shadow_node_visits;
 	st.tri_tests = ctr[RTX_C_TRIS] + ctr[RTX_C_STRIS];
 	st.sphere_tests = ctr[RTX_C_SPHERES] + ctr[RTX_C_SSPHERES];
@@ -1593,6 +1625,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow cull %lld is not 0, 1 or 2", (long long)value);
 		c->opt_cull = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_POINT:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow point masks %lld is not 0 or 1", (long long)value);
+		c->opt_point = (int)value;
+		return RTX_OK;
 	}
 	return fail(RTX_ERR_ARG, "unknown option %d", option);
 }
@@ -1621,6 +1658,14 @@ extern "C" int rtx_get_stats(const rtx_ctx *c, rtx_stats *out)
 	if (!c || !out)
 		return fail(RTX_ERR_ARG, "null argument");
 	*out = c->stats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_get_point_stats(const rtx_ctx *c, rtx_point_stats *out)
+{
+	if (!c || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = c->pstats;
 	return RTX_OK;
 }
 

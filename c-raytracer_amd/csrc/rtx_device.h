@@ -259,6 +259,13 @@ typedef struct DScene {
 	                        * the tree lies in one.  Null / 0: no cull */
 	uint32_t num_cull;
 	uint32_t cull_slots;   /* RTX_OPT_SHADOW_CULL 2: the lane-slot path culls too (cone_mask_lane) */
+	const float *lsph;     /* k_shadow's per-point masks (RTX_OPT_SHADOW_POINT): the bounding spheres {world centre,
+	                        * radius} of the records k_shadow tests one by one (`lin`, or the emitters the 8-wide
+	                        * tree leaves out), in their order, padded like `cull`; null when there are none or
+	                        * more than RTX_CULL_MAX */
+	uint32_t num_lsph;
+	uint32_t point;        /* RTX_OPT_SHADOW_POINT (and RTX_OPT_SHADOW_CULL not 0): planes and listed records are
+	                        * decided once per shade point of the wave-uniform path */
 } DScene;
 #define RTX_CULL_MAX 64
 
@@ -328,6 +335,9 @@ enum {
 	RTX_C_FARS,         /* count mode: shadow rays from far shade points (walked from the light end) */
 	RTX_C_SSPILL,       /* count mode, 8-wide walk: lane-stack pushes beyond the LDS entries (HBM) */
 	RTX_C_SCLEAR,       /* count mode: shadow rays of packets the cone cull let skip the walk */
+	RTX_C_SPSKIP,       /* count mode: plane tests a shade point's plane mask let skip */
+	RTX_C_SLSKIP,       /* count mode: listed-object tests its listed-object mask let skip */
+	RTX_C_SPCLEAR,      /* count mode: shadow rays of all-clear shade points (clear_run) */
 	RTX_C_N
 };
 

@@ -65,6 +65,7 @@ struct rtx_group {
 	std::vector<size_t> buf_cap;   /* capacity of d_buf[r] in records */
 	std::vector<size_t> recv_cap;  /* capacity of d_recv[r] in records */
 	rtx_stats stats{};
+	rtx_point_stats pstats{};
 };
 
 extern "C" void rtx_group_close(rtx_group *g)
@@ -496,6 +497,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 
 	/* statistics: counts summed, times of the slowest device */
 	rtx_stats s = c0->stats;
+	rtx_point_stats ps = c0->pstats;
 	for (int r = 1; r < n; r++) {
 		const rtx_stats &o = g->ctx[r]->stats;
 		s.closest_rays += o.closest_rays;
@@ -519,6 +521,9 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 		s.far_shadow_rays += o.far_shadow_rays;
 		s.shadow_stack_spills += o.shadow_stack_spills;
 		s.shadow_cone_clear += o.shadow_cone_clear;
+		ps.shadow_plane_skipped += g->ctx[r]->pstats.shadow_plane_skipped;
+		ps.shadow_lin_skipped += g->ctx[r]->pstats.shadow_lin_skipped;
+		ps.shadow_point_clear += g->ctx[r]->pstats.shadow_point_clear;
 		s.waves += o.waves;
 		s.chunks += o.chunks;
 		s.kernel_ms = std::max(s.kernel_ms, o.kernel_ms);
@@ -532,6 +537,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	s.gather_ms = n > 1 || g->rccl_self ? gather_ms : 0.0;
 	s.devices = (uint32_t)n;
 	g->stats = s;
+	g->pstats = ps;
 	return RTX_OK;
 }
 
@@ -540,6 +546,24 @@ extern "C" int rtx_group_get_stats(const rtx_group *g, rtx_stats *out)
 	if (!g || !out)
 		return fail(RTX_ERR_ARG, "null argument");
 	*out = g->stats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_get_point_stats(const rtx_group *g, rtx_point_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = g->pstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (r < 0 || r >= g->n)
+		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
+	*out = g->ctx[r]->pstats;
 	return RTX_OK;
 }
 

@@ -85,6 +85,7 @@ struct rtx_ctx {
 	DW8S *d_w8s = nullptr;
 	uint32_t *d_w8spill = nullptr; /* k_shadow lane-stack spill of deep 8-wide trees (DScene.w8spill) */
 	float4 *d_cull = nullptr;      /* the 8-wide tree's top-level bounding spheres (DScene.cull) */
+	float4 *d_lsph = nullptr;      /* the listed records' bounding spheres (DScene.lsph) */
 	size_t w8spill_bytes = 0;
 	DScene scene{};
 	bool have_scene = false;
@@ -120,6 +121,7 @@ struct rtx_ctx {
 	float *d_rgb = nullptr, *d_z = nullptr;
 	size_t fb_pixels = 0;
 	rtx_stats stats{};
+	rtx_point_stats pstats{}; /* rtx_get_point_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
 	unsigned long long *d_rctr = nullptr;
 	void *d_qrays = nullptr, *d_qhits = nullptr;
@@ -139,6 +141,7 @@ struct rtx_ctx {
 	uint32_t opt_rays_grab = 0;   /* RTX_OPT_RAYS_GRAB: packets per k_rays queue grab (0: automatic) */
 	uint32_t opt_rays_queues = 0; /* RTX_OPT_RAYS_QUEUES: k_rays packet queues (0: automatic) */
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
+	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	uint32_t mem_share = 1;   /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */
 };

@@ -32,4 +32,32 @@ __host__ __device__ static inline uint32_t rtx_quantise8(uint32_t q16, uint32_t 
 	return lo | (hi << 8);
 }
 
+/* The bounding sphere {centre, radius} of a record k_shadow tests one by one (rtx_device.h
+ * DEmitter: a sphere itself, a triangle's circumscribing sphere about its centroid), formed in
+ * double and padded like the cone cull's tree spheres (rtx_api.cpp build_cull) for the kernel's
+ * float test (rtx_shadow.hip point_masks). */
+__host__ __device__ static inline void rtx_record_sphere(bool sphere, const float *p0, const float *p1, const float *p2, float radius,
+							 float out[4])
+{
+	double c[3], r = 0, m = 0;
+	for (int a = 0; a < 3; a++)
+		c[a] = sphere ? (double)p0[a] : ((double)p0[a] + (double)p1[a] + (double)p2[a]) / 3.0;
+	if (sphere) {
+		r = fabs((double)radius);
+	} else {
+		const float *v[3] = { p0, p1, p2 };
+		for (int k = 0; k < 3; k++) {
+			double d2 = 0;
+			for (int a = 0; a < 3; a++)
+				d2 += ((double)v[k][a] - c[a]) * ((double)v[k][a] - c[a]);
+			r = fmax(r, sqrt(d2));
+		}
+	}
+	for (int a = 0; a < 3; a++) {
+		m = fmax(m, fabs(c[a]));
+		out[a] = (float)c[a];
+	}
+	out[3] = (float)(r * (1 + 1e-5) + 1e-5 * m + 1e-6);
+}
+
 #endif

@@ -162,7 +162,10 @@ struct ShadowCount {
 	u64 unif;      /* 8-wide walk: wave steps with one node for all walking lanes (scalar path) */
 	u64 far;       /* rays from far shade points, walked from the light end (RTX_SP_FAR) */
 	u64 spills;    /* 8-wide walk: lane-stack pushes beyond the LDS entries (to DScene.w8spill in HBM) */
-	u64 clear;     /* rays of packets the cone cull let skip the walk (cone_clear) */
+	u64 clear;     /* rays of packets the cone cull let skip the walk (point_masks) */
+	u64 pskip;     /* plane tests the point's plane mask let skip (point_masks) */
+	u64 lskip;     /* listed-object tests its listed-object mask let skip */
+	u64 pclear;    /* rays of all-clear points (clear_run) */
 };
 
 /* one primitive record (a, b, c = its first 48 bytes) against this lane's shadow ray
@@ -801,9 +804,12 @@ const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi
 	uint32_t n_sp, per_wave, slot_b, slot_lg;
 	int32_t rng, attenuation, reflection;
 	float att_offset;
-	const float4 *cull;   /* DScene.cull: the 8-wide tree's second-level bounding spheres (cone_clear) */
+	const float4 *cull;   /* DScene.cull: the 8-wide tree's second-level bounding spheres (point_masks) */
 	uint32_t num_cull;    /* 0: no cull (RTX_OPT_SHADOW_CULL off, or no such tree) */
 	uint32_t cull_slots;  /* the lane-slot path culls too (RTX_OPT_SHADOW_CULL 2) */
+	const float4 *lsph;   /* DScene.lsph: the bounding spheres of the `lin` records (point_masks) */
+	uint32_t num_lsph;    /* num_lin when they are there, else 0 */
+	uint32_t point;       /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 };
 
 __device__ __forceinline__ void reread_barrier() { asm volatile("" ::: "memory"); }
@@ -870,25 +876,42 @@ __device__ __forceinline__ float sh_pow(float x, float y)
 /* the attenuation factor of a light sample at distance ldist (render.c:217-222), formed before
  * the walk so one float, not ldist and dsq, lives across it (the product with the transmittance
  * after the walk is the same operation in the same order) */
-__device__ __forceinline__ float sample_att(const KShadow &ks, float ldist, float dsq)
+__device__ __forceinline__ float sample_att_of(int32_t att, float att_offset, float ldist, float dsq)
 {
-	const int32_t att = (int32_t)uni((uint32_t)ks.attenuation);
 	if (att == RTX_ATT_LIN)
-		return sh_rcp(ks.att_offset + ldist);
+		return sh_rcp(att_offset + ldist);
 	if (att == RTX_ATT_SQR)
-		return sh_rcp(ks.att_offset + dsq);
+		return sh_rcp(att_offset + dsq);
 	return 1.f;
 }
+__device__ __forceinline__ float sample_att(const KShadow &ks, float ldist, float dsq)
+{
+	return sample_att_of((int32_t)uni((uint32_t)ks.attenuation), ks.att_offset, ldist, dsq);
+}
 
-/* direct-lighting terms of one unblocked light sample (render.c:199-228), read after the walk */
+/* direct-lighting terms of one unblocked light sample (render.c:199-228) from the shade point's
+ * normal n, view direction dir, diffuse colour kd and its material's ks3 / shin */
+__device__ __forceinline__ f3 shade_terms(int32_t att, int32_t refl, f3 n, f3 dir, f3 kd, f3 ks3, float shin, f3 ldir, f3 li, float attf)
+{
+	const float a = dot3(ldir, n);
+	if (att != RTX_ATT_NONE)
+		li = mul3s(li, attf);
+	const f3 diff = mul3s(mul3v(kd, li), fmaxf(0.f, a));
+	float sm;
+	if (refl == RTX_BLINN)
+		sm = -dot3(n, norm3(add3(mul3s(ldir, -1.f), dir)));
+	else
+		sm = -dot3(sub3(mul3s(n, 2.f * a), ldir), dir);
+	const f3 spec = mul3s(mul3v(ks3, li), fmaxf(0.f, sh_pow(sm, shin)));
+	return add3(diff, spec);
+}
+
+/* the same of the shade point `rec`, read after the walk */
 template <bool UNI>
 __device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, f3 ldir, f3 li, float attf)
 {
 	const float4 q1 = sp_field<UNI>(rec, 1), q2 = sp_field<UNI>(rec, 2), q3 = sp_field<UNI>(rec, 3);
 	const f3 n = mk3(q1.x, q1.y, q1.z), dir = mk3(q2.x, q2.y, q2.z);
-	const float a = dot3(ldir, n);
-	if ((int32_t)uni((uint32_t)ks.attenuation) != RTX_ATT_NONE)
-		li = mul3s(li, attf);
 	f3 ks3;
 	float shin;
 	if (UNI) { /* the material of a wave-uniform record: scalar reads */
@@ -900,25 +923,16 @@ __device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, 
 		ks3 = ld3(m.ks);
 		shin = m.shininess;
 	}
-	const f3 diff = mul3s(mul3v(mk3(q3.x, q3.y, q3.z), li), fmaxf(0.f, a));
-	float sm;
-	if ((int32_t)uni((uint32_t)ks.reflection) == RTX_BLINN)
-		sm = -dot3(n, norm3(add3(mul3s(ldir, -1.f), dir)));
-	else
-		sm = -dot3(sub3(mul3s(n, 2.f * a), ldir), dir);
-	const f3 spec = mul3s(mul3v(ks3, li), fmaxf(0.f, sh_pow(sm, shin)));
-	return add3(diff, spec);
+	return shade_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, mk3(q3.x, q3.y, q3.z), ks3,
+			   shin, ldir, li, attf);
 }
 
-/* the light point of sample j of emitter number e, E (object.c:293-304, 403-419: stratified per
- * the rng mode), its shadow ray's direction and length, and the sample's intensity */
-__device__ __forceinline__ void emitter_sample(const KShadow &ks, const DEmitter &E, uint32_t e, uint32_t j, uint32_t ka, uint32_t kb,
-					       f3 p, f3 &ldir, float &ldist, float &dsq, f3 &li)
+/* the light point of sample j of emitter E from its draws u1, u2 (object.c:293-304, 403-419:
+ * stratified per the rng mode), its shadow ray's direction and length, and the sample's intensity */
+__device__ __forceinline__ void sample_ray(int32_t rng, const DEmitter &E, uint32_t j, float u1, float u2, f3 p, f3 &ldir, float &ldist,
+					   float &dsq, f3 &li)
 {
-	float u1 = 0.5f, u2 = 0.5f;
-	if (uni(ks.rng) != RTX_RNG_CONST) /* the key already carries the seed (rtx_key_pixel) */
-		rtx_draw2(key_of(ka, kb), e, j, &u1, &u2);
-	if (uni(ks.rng) == RTX_RNG_STRAT) /* stratum j of the emitter's lights (IEEE, as the oracle) */
+	if (rng == RTX_RNG_STRAT) /* stratum j of the emitter's lights (IEEE, as the oracle) */
 		u1 = ((float)j + u1) / (float)E.num_lights;
 	const f3 lp = light_point_sh(E, p, u1, u2);
 	const f3 dv = sub3(lp, p);
@@ -926,6 +940,16 @@ __device__ __forceinline__ void emitter_sample(const KShadow &ks, const DEmitter
 	ldist = RTX_SH_FASTSQRT ? __builtin_amdgcn_sqrtf(dsq) : sqrtf(dsq); /* mag3(dv) */
 	ldir = mul3s(dv, sh_rcp(ldist));
 	li = ld3(E.li);
+}
+
+/* the same of sample j of emitter number e, E, its draws made here */
+__device__ __forceinline__ void emitter_sample(const KShadow &ks, const DEmitter &E, uint32_t e, uint32_t j, uint32_t ka, uint32_t kb,
+					       f3 p, f3 &ldir, float &ldist, float &dsq, f3 &li)
+{
+	float u1 = 0.5f, u2 = 0.5f;
+	if (uni(ks.rng) != RTX_RNG_CONST) /* the key already carries the seed (rtx_key_pixel) */
+		rtx_draw2(key_of(ka, kb), e, j, &u1, &u2);
+	sample_ray(uni(ks.rng), E, j, u1, u2, p, ldir, ldist, dsq, li);
 }
 
 /* an emitter record read through the scalar cache (every lane reads the same one) */
@@ -967,24 +991,15 @@ __device__ __forceinline__ QBvh make_qbvh(const KShadow &ks, const uint4 *top_q,
 	return Q;
 }
 
-/* The cone cull of a packet of one shade point's samples of one emitter: every shadow ray of the
- * packet runs from p to a point of the emitter, so it lies in the cone from p around the emitter's
- * bounding sphere (below), cut at the sphere's far side.  Lane k tests the bounding sphere k of the 8-wide tree's second level
- * (DScene.cull, world space): centre distance t along the axis, e off it; the sphere misses the
- * cone when e cos(a) - t sin(a) > r or it lies wholly before p or beyond the light.  r is padded
- * by 2e-5 of the coordinates' and distances' magnitudes, far above the rays' float rounding, so a
- * clear packet is one whose walks could reach no primitive: skipping them changes no bit of the
- * image (test_gpu_cone_cull_is_invisible).  True when no lane's sphere meets the cone. */
-__device__ __forceinline__ bool cone_clear(const KShadow &ks, const DEmitter &E, f3 p)
+/* The cone cull and the per-point masks (point_masks below): every shadow ray of a shade point p
+ * toward an emitter runs from p to a point of the emitter, so it lies in the cone from p around the
+ * emitter's bounding sphere, cut at the sphere's far side; what the cone cannot meet, no sample's
+ * ray can. */
+__device__ __forceinline__ void emitter_sphere(const DEmitter &E, f3 &lc, float &lr)
 {
-	const uint32_t n = uni(ks.num_cull);
-	if (!n)
-		return false;
 	/* the emitter's bounding sphere: a sphere light itself (its light points are c + ld with |ld|
 	 * the radius to a few ulp, light_point_sh), a triangle's circumscribing sphere about its
 	 * centroid (its light points lie in it); padded by 1e-4 of the radius and 1e-6 of |c| */
-	f3 lc;
-	float lr;
 	if (E.type == RTX_SPHERE) {
 		lc = ld3(E.p0);
 		lr = E.radius;
@@ -994,38 +1009,135 @@ __device__ __forceinline__ bool cone_clear(const KShadow &ks, const DEmitter &E,
 		lr = sqrtf(fmaxf(fmaxf(magsqr3(sub3(a, lc)), magsqr3(sub3(b, lc))), magsqr3(sub3(c, lc))));
 	}
 	lr = lr * 1.0001f + 1e-6f * fmaxf(fmaxf(fabsf(lc.x), fabsf(lc.y)), fabsf(lc.z));
-	const f3 ax0 = sub3(lc, p);
-	const float L = sqrtf(magsqr3(ax0));
-	if (!(L > 1.01f * lr)) /* the point at or inside the light's sphere: no cone */
-		return false;
-	const f3 ax = mul3s(ax0, 1.f / L);
-	const float sn = lr / L, cs = sqrtf(fmaxf(0.f, 1.f - sn * sn));
-	const float mag = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)) + fmaxf(fmaxf(fabsf(lc.x), fabsf(lc.y)), fabsf(lc.z));
-	bool meets = false;
-	const uint32_t k = lane_id();
-	if (k < n) {
-		const float4 sp = ldg4((const char *)(unip(ks.cull) + k), 0);
-		const f3 v = sub3(mk3(sp.x, sp.y, sp.z), p);
-		const float vv = magsqr3(v), t = dot3(v, ax);
-		const float e = sqrtf(fmaxf(0.f, vv - t * t));
-		const float br = sp.w + 2e-5f * (mag + sqrtf(vv) + L + lr);
-		meets = vv <= br * br || (t >= -br && t <= L + lr + br && e * cs - t * sn <= br);
-	}
-	return !ballot(meets);
 }
 
-/* the emitters (bit e, e < 64) whose cone from shade point p meets no top-level box of the tree:
- * formed once per point of the wave-uniform path, before its packets (a far point: none) */
-__device__ __forceinline__ u64 cone_mask(const KShadow &ks, f3 p, bool far)
+/* the cone from p around the emitter's sphere (lc, lr), L = |lc - p| > 1.01 lr */
+struct Cone {
+	f3 ax;
+	float L, lr, sn, cs, mag;
+};
+__device__ __forceinline__ Cone cone_of(f3 p, f3 lc, float lr, f3 ax0, float L)
 {
-	if (!uni(ks.num_cull) || far)
-		return 0ull;
+	Cone c;
+	c.ax = mul3s(ax0, 1.f / L);
+	c.L = L;
+	c.lr = lr;
+	c.sn = lr / L;
+	c.cs = sqrtf(fmaxf(0.f, 1.f - c.sn * c.sn));
+	c.mag = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)) + fmaxf(fmaxf(fabsf(lc.x), fabsf(lc.y)), fabsf(lc.z));
+	return c;
+}
+/* does the bounding sphere sp = {centre, radius} meet the cone from p?  REC: the sphere of a listed
+ * record, padded by 1e-3 of its distance besides: hit_sphere's discriminant (|rel|^2 - r^2 against
+ * b^2, each rounded at 2^-24 |rel|^2) is sure to be negative only for a ray that passes the sphere
+ * by more than about 6e-4 |rel|, however small the sphere */
+template <bool REC> __device__ __forceinline__ bool cone_meets(const Cone &c, f3 p, float4 sp)
+{
+	const f3 v = sub3(mk3(sp.x, sp.y, sp.z), p);
+	const float vv = magsqr3(v), t = dot3(v, c.ax);
+	const float e = sqrtf(fmaxf(0.f, vv - t * t));
+	float br = sp.w + 2e-5f * (c.mag + sqrtf(vv) + c.L + c.lr);
+	if (REC)
+		br += 1e-3f * sqrtf(vv);
+	return vv <= br * br || (t >= -br && t <= c.L + c.lr + br && e * c.cs - t * c.sn <= br);
+}
+
+/* Plane (n, dd, eps) is clear for shade point p and the emitter in the padded sphere (lc, lr), L =
+ * |lc - p|: no ray from p to a point lp of the sphere can pass plane_blocks.  With s = dd - n.p (the
+ * very expression plane_blocks forms) and h = n.lp - dd in [sc - rho, sc + rho], rho = lr |n|, every
+ * such ray has a dist = h + s and t / dist = s / (h + s).  The sphere must lie strictly on one
+ * side (|sc| - rho > m); then either
+ *  - same side: p lies on the sphere's side too, by more than m: t < 0, or t > dist by the factor
+ *    1 + (|sc| - rho) / |s|;
+ *  - on or near the plane: |s| (L + lr) <= eps (|sc| - rho - |s|), so |t| = |s| / |a| <= eps and
+ *    t > eps fails.
+ * m = 2e-5 (|dd| + |n| (2 (|p| + |lc|) + L + lr)), max norms: some sixty times the float rounding of
+ * s, sc, a dist (n.(lp - p), whose error is absolute in the coordinates) and of the quotients (1 ulp
+ * each: v_rcp_f32, v_sqrt_f32), as the cone test's pads are.  (KAT: RTX_KAT_PLANE_CLEAR) */
+__device__ __forceinline__ bool plane_clear(f3 n, float dd, float eps, f3 p, f3 lc, float lr, float L)
+{
+	if (!(eps > 0.f))
+		return false;
+	const float s = dd - dot3(n, p);
+	const float nn = sqrtf(magsqr3(n));
+	const float sc = dot3(n, lc) - dd;
+	const float as = fabsf(s), reach = L + lr;
+	const float pm = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z)), lm = fmaxf(fmaxf(fabsf(lc.x), fabsf(lc.y)), fabsf(lc.z));
+	const float m = 2e-5f * (fabsf(dd) + nn * (2.f * (pm + lm) + reach));
+	const float hmin = fabsf(sc) - lr * nn - m;
+	if (!(hmin > 0.f)) /* the sphere touches or straddles the plane (or a NaN) */
+		return false;
+	if (as > m && (sc > 0.f) == (s < 0.f))
+		return true;
+	return as * reach * 1.0001f <= eps * (hmin - as);
+}
+
+/* what point_masks decides once per shade point of the wave-uniform path, bit e for emitter e < 64 */
+struct PointMasks {
+	u64 cone; /* the cone toward e meets no top-level box of the tree (point_masks) */
+	u64 pln;  /* every plane is clear for e (plane_clear) */
+	u64 lin;  /* the cone toward e meets no listed record's bounding sphere (the record of e itself apart) */
+	u64 smp;  /* the point samples e (e is not the object the point lies on) */
+};
+
+/* The masks of shade point p on object obj, formed before its packets (a far point: none).  The cone
+ * test of one emitter runs over the lanes: lane k < n tests bounding sphere k of the 8-wide tree's
+ * second level (DScene.cull, world space), then lane k < nr the listed record k's sphere
+ * (DScene.lsph; at most 64, else the records are never clear): centre distance t
+ * along the axis, e off it; a sphere misses the cone when e cos(a) - t sin(a) > r or it lies wholly
+ * before p or beyond the light.  r is padded by 2e-5 of the coordinates' and distances' magnitudes,
+ * far above the rays' float rounding, so a clear packet is one whose walks / record tests could reach
+ * no primitive: skipping them changes no bit of the image (test_gpu_cone_cull_is_invisible,
+ * tests/test_gpu_pointclear.py). */
+__device__ __forceinline__ PointMasks point_masks(const KShadow &ks, f3 p, uint32_t obj, bool far)
+{
+	PointMasks m = { 0ull, 0ull, 0ull, 0ull };
+	const bool pt = uni(ks.point) != 0;
+	const uint32_t n = uni(ks.num_cull);
+	if ((!n && !pt) || far)
+		return m;
 	const DEmitter *emitters = unip(ks.emitters);
 	const uint32_t ne = min(uni(ks.num_emitters), 64u);
-	u64 m = 0ull;
-	for (uint32_t e = 0; e < ne; e++)
-		if (cone_clear(ks, emitter_uni(emitters + e), p))
-			m |= 1ull << e;
+	const uint32_t num_lin = uni(ks.num_lin), num_planes = uni(ks.num_planes);
+	const uint32_t nr = pt ? min(uni(ks.num_lsph), (uint32_t)WAVE) : 0u;
+	const bool lin_ok = pt && nr == num_lin; /* every listed record has its sphere (or there is none) */
+	for (uint32_t e = 0; e < ne; e++) {
+		const DEmitter E = emitter_uni(emitters + e);
+		const u64 bit = 1ull << e;
+		if (E.obj != obj)
+			m.smp |= bit;
+		f3 lc;
+		float lr;
+		emitter_sphere(E, lc, lr);
+		const f3 ax0 = sub3(lc, p);
+		const float L = sqrtf(magsqr3(ax0));
+		if (pt) {
+			bool pc = true;
+			for (uint32_t i = 0; i < num_planes; i++) { /* plane records are wave-uniform: s_load */
+				const auto *pl = cptr(unip(ks.planes)) + i;
+				pc = plane_clear(mk3(pl->n[0], pl->n[1], pl->n[2]), pl->d, pl->eps, p, lc, lr, L) && pc;
+			}
+			if (pc)
+				m.pln |= bit;
+			if (!num_lin)
+				m.lin |= bit;
+		}
+		if (!(L > 1.01f * lr)) /* the point at or inside the light's sphere: no cone */
+			continue;
+		if (!n && !nr)
+			continue;
+		const Cone c = cone_of(p, lc, lr, ax0, L);
+		const uint32_t k = lane_id();
+		if (n && !ballot(k < n && cone_meets<false>(c, p, ldg4((const char *)(unip(ks.cull) + min(k, n - 1u)), 0))))
+			m.cone |= bit;
+		/* the records in a pass of their own: the bench scene's tree alone fills the 64 lanes */
+		if (lin_ok && nr) {
+			const uint32_t kr = min(k, nr - 1u);
+			const uint32_t ro = gptr((const uint32_t *)(unip(ks.lin) + kr))[0]; /* DEmitter.obj */
+			if (!ballot(k < nr && ro != E.obj && cone_meets<true>(c, p, ldg4((const char *)(unip(ks.lsph) + kr), 0))))
+				m.lin |= bit;
+		}
+	}
 	return m;
 }
 
@@ -1081,6 +1193,20 @@ __device__ __forceinline__ uint32_t cone_mask_lane(const KShadow &ks, f3 p, bool
 	return m;
 }
 
+/* count mode: the plane and listed-object tests that `na` rays toward emitter object eobj skip */
+__device__ __forceinline__ void count_skips(const KShadow &ks, uint32_t na, uint32_t eobj, bool pclr, bool lclr, ShadowCount &sc)
+{
+	if (pclr)
+		sc.pskip += (u64)na * uni(ks.num_planes);
+	if (lclr) {
+		const auto *lin = cptr(unip(ks.lin));
+		uint32_t others = 0;
+		for (uint32_t i = 0; i < uni(ks.num_lin); i++)
+			others += lin[i].obj != eobj ? 1u : 0u;
+		sc.lskip += (u64)na * others;
+	}
+}
+
 /* one light sample per lane of the shade point `rec` (render.c:170-229): the light point of
  * sample idx (emitters in scene order, the hit object skipped), its shadow ray, attenuation
  * and Phong / Blinn.  Argument-block fields are read from LDS behind reread barriers. */
@@ -1121,14 +1247,20 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	f3 ldir, li;
 	float ldist, dsq;
 	uint32_t eobj;
-	bool clear = false; /* UNI: the packet's cone meets no top-level box of the tree (cone_clear) */
+	bool clear = false; /* UNI: the packet's cone meets no top-level box of the tree (point_masks) */
+	bool pclr = false, rclr = false; /* UNI: its planes / listed records are clear */
 	if (!ballot(act && e != lead)) {
 		const DEmitter Eu = emitter_uni(emitters + lead);
 		emitter_sample(ks, Eu, lead, j, __float_as_uint(q4.y), __float_as_uint(q4.z), p, ldir, ldist, dsq, li);
 		eobj = Eu.obj;
-		/* the point's cone_mask, kept in the wave's LDS table (a 64-bit mask in SGPRs across the walk
+		/* the point's cone mask, kept in the wave's LDS table (a 64-bit mask in SGPRs across the walk
 		 * cost the walk a spilled register) */
-		clear = UNI && WALK == WALK_W8 && ((uni(cmask[lead >> 5]) >> (lead & 31u)) & 1u);
+		clear = UNI && WALK == WALK_W8 && lead < 64u && ((uni(cmask[lead >> 5]) >> (lead & 31u)) & 1u);
+		/* ... and its plane and listed-object masks (point_masks): the packet runs neither loop */
+		if (UNI && lead < 64u) { /* the masks hold emitters 0..63 */
+			pclr = (uni(cmask[2 + (lead >> 5)]) >> (lead & 31u)) & 1u;
+			rclr = (uni(cmask[4 + (lead >> 5)]) >> (lead & 31u)) & 1u;
+		}
 	} else {
 		const DEmitter &E = emitters[e];
 		emitter_sample(ks, E, e, j, __float_as_uint(q4.y), __float_as_uint(q4.z), p, ldir, ldist, dsq, li);
@@ -1144,9 +1276,12 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	const bool have_tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK && !clear;
 	if (COUNT && clear)
 		sc.clear += (u64)popc64(ballot(act));
-	const bool blocked = shadow_query<COUNT, WALK, LA>(Q, unip(ks.recs), unip(ks.mats), unip(ks.planes), uni(ks.num_planes),
-						 unip(ks.lin), uni(ks.num_lin), have_tree, ks.tf, act, far != 0, p, ldir, ldist, eobj, li,
-							 sc);
+	if (COUNT && UNI)
+		count_skips(ks, popc64(ballot(act)), eobj, pclr, rclr, sc);
+	const bool blocked = shadow_query<COUNT, WALK, LA>(Q, unip(ks.recs), unip(ks.mats), unip(ks.planes),
+							 (UNI && pclr) ? 0u : uni(ks.num_planes), unip(ks.lin),
+							 (UNI && rclr) ? 0u : uni(ks.num_lin), have_tree, ks.tf, act, far != 0, p, ldir,
+							 ldist, eobj, li, sc);
 	reread_barrier();
 	if (!UNI && RTX_SH_RECAFTER) {
 		asm volatile("" : "+v"(sidv));
@@ -1156,6 +1291,76 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	if (act && !blocked)
 		contribution = shade_light<UNI && RTX_SH_SPUNI>(ks, rec, ldir, li, attf);
 	return contribution;
+}
+
+/* The packets of an all-clear shade point `rec` (point_masks: for every emitter it samples, the
+ * tree part, the planes and the listed records are clear), from sample `base` on: every sample is
+ * unblocked and its intensity untouched, so a packet inside one emitter's samples is light_sample
+ * without shadow_query: the same float operations in the same order per sample, each lane adding
+ * its samples to acc in packet order.  The shade point's fields, its material, the argument-block
+ * fields and, per emitter, the emitter's record and the (key, stream) mix of its draws are formed
+ * once here, not per packet, and nothing is re-read behind a barrier (there is no walk to keep
+ * registers free for).  Returns the first packet that straddles two emitters (the caller runs it
+ * through light_sample), or one at or beyond nl. */
+template <bool COUNT, int WALK>
+__device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *rec, uint32_t nl, uint32_t base, f3 &acc, ShadowCount &sc,
+					      const uint32_t *cmask)
+{
+	const float4 q0 = sp_field<true>(rec, 0), q1 = sp_field<true>(rec, 1), q2 = sp_field<true>(rec, 2), q3 = sp_field<true>(rec, 3),
+		     q4 = sp_field<true>(rec, 4);
+	const f3 p = mk3(q0.x, q0.y, q0.z), n = mk3(q1.x, q1.y, q1.z), dir = mk3(q2.x, q2.y, q2.z), kd = mk3(q3.x, q3.y, q3.z);
+	const uint32_t obj = __float_as_uint(q4.x) & ~RTX_SP_FAR;
+	const uint64_t key = key_of(__float_as_uint(q4.y), __float_as_uint(q4.z));
+	const auto &mat = cptr(unip(ks.mats))[__float_as_uint(q3.w)];
+	const f3 ks3 = mk3(mat.ks[0], mat.ks[1], mat.ks[2]);
+	const float shin = mat.shininess;
+	const int32_t rng = (int32_t)uni((uint32_t)ks.rng), att = (int32_t)uni((uint32_t)ks.attenuation),
+		      refl = (int32_t)uni((uint32_t)ks.reflection);
+	const float att_offset = __uint_as_float(uni(__float_as_uint(ks.att_offset)));
+	const DEmitter *emitters = unip(ks.emitters);
+	const auto *EM = cptr(emitters);
+	const uint32_t ne = uni(ks.num_emitters);
+	/* emitter cur's samples are [start, end); nxt: the next emitter to look at */
+	uint32_t nxt = 0, cur = 0, start = 0, end = 0;
+	while (base < nl) {
+		while (base >= end && nxt < ne) {
+			const uint32_t eo = EM[nxt].obj, enl = EM[nxt].num_lights;
+			if (eo != obj) {
+				cur = nxt;
+				start = end;
+				end = start + enl;
+			}
+			nxt++;
+		}
+		if (base >= end || min(base + WAVE, nl) > end) /* no emitter found (never), or a straddling packet */
+			break;
+		const DEmitter E = emitter_uni(emitters + cur);
+		const uint64_t mix = rtx_draw_mix(key, cur);
+		uint32_t rays = 0;
+		for (; base < nl && min(base + WAVE, nl) <= end; base += WAVE) {
+			const uint32_t idx = base + lane_id(), j = idx - start;
+			const bool act = idx < nl;
+			float u1 = 0.5f, u2 = 0.5f;
+			if (rng != RTX_RNG_CONST)
+				rtx_draw2_mixed(mix, j, &u1, &u2);
+			f3 ldir, li;
+			float ldist, dsq;
+			sample_ray(rng, E, j, u1, u2, p, ldir, ldist, dsq, li);
+			const float attf = sample_att_of(att, att_offset, ldist, dsq);
+			f3 contribution = mk3(0.f, 0.f, 0.f);
+			if (act)
+				contribution = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf);
+			acc = add3(acc, contribution);
+			if (COUNT)
+				rays += popc64(ballot(act));
+		}
+		if (COUNT) {
+			if (WALK == WALK_W8 && ((uni(cmask[cur >> 5]) >> (cur & 31u)) & 1u))
+				sc.clear += rays;
+			count_skips(ks, rays, E.obj, true, true, sc);
+		}
+	}
+	return base;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1189,7 +1394,8 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 		uint32_t nls[WAVE];     /* shadow rays of each shade point */
 		uint32_t sid[WAVE];     /* each shade point's index in the record array */
 		float Ls[3][WAVE];      /* per shade point light sum, in packet order */
-		uint32_t cm[2];         /* the current point's cone_mask (wave-uniform path) */
+		uint32_t cm[8];         /* the current point's masks (wave-uniform path, point_masks): cone, planes, listed
+		                         * objects (two words each), all-clear flag, unused */
 		uint8_t clr[WAVE];      /* each shade point's cone_mask_lane, emitters 0..7 (lane-slot path; a byte:
 		                         * the LDS of two workgroups must still fit a CU) */
 	};
@@ -1219,7 +1425,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 	 * scene6's k_shadow took 1083.4 against 1074.8 ms) */
 	constexpr bool SC = RTX_SH_SLOTCULL && WALK == WALK_W8 && (PATH == 3 || PATH == 0);
 	lds_u32 *stk = (lds_u32 *)&wstk[wv][0][LA ? 0u : lane_id()];
-	ShadowCount sc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	ShadowCount sc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 	u64 rays_total = 0;
 	for (;;) {
 		reread_barrier();
@@ -1256,7 +1462,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 				reread_barrier();
 				const uint32_t nl = uni(nls[k]);
 				const float4 *rec = unip(ks.sp) + (size_t)uni(sid[k]) * SPREC;
-				if (WALK == WALK_W8) {
+				{
 					/* the point through vector loads made uniform, not the scalar loads light_sample
 					 * makes: shared with them, the point was live from here and the compiler hoisted
 					 * the far path's double-precision copies of it out of the packet loop and
@@ -1264,15 +1470,37 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 					const float4 q0 = ldg4(rec, 0), q4 = ldg4(rec, 64);
 					const f3 pu = mk3(__uint_as_float(uni(__float_as_uint(q0.x))), __uint_as_float(uni(__float_as_uint(q0.y))),
 							  __uint_as_float(uni(__float_as_uint(q0.z))));
-					const u64 m = cone_mask(ks, pu, (uni(__float_as_uint(q4.x)) & RTX_SP_FAR) != 0);
+					const uint32_t ou = uni(__float_as_uint(q4.x));
+					PointMasks m = { 0ull, 0ull, 0ull, 0ull };
+					if (WALK == WALK_W8 || uni(ks.point))
+						m = point_masks(ks, pu, ou & ~RTX_SP_FAR, (ou & RTX_SP_FAR) != 0);
+					/* all-clear: every emitter the point samples is clear of the tree (or there is none),
+					 * the planes and the listed records */
+					const bool tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK;
+					const u64 ok = m.pln & m.lin & (tree ? m.cone : ~0ull);
+					const bool ac = uni(ks.point) != 0 && !(ou & RTX_SP_FAR) && uni(ks.num_emitters) <= 64u && !(m.smp & ~ok);
 					if (lane_id() == 0) {
-						wt_w[wv].cm[0] = (uint32_t)m;
-						wt_w[wv].cm[1] = (uint32_t)(m >> 32);
+						wt_w[wv].cm[0] = (uint32_t)m.cone;
+						wt_w[wv].cm[1] = (uint32_t)(m.cone >> 32);
+						wt_w[wv].cm[2] = (uint32_t)m.pln;
+						wt_w[wv].cm[3] = (uint32_t)(m.pln >> 32);
+						wt_w[wv].cm[4] = (uint32_t)m.lin;
+						wt_w[wv].cm[5] = (uint32_t)(m.lin >> 32);
+						wt_w[wv].cm[6] = ac ? 1u : 0u;
 					}
 					lds_sync();
 				}
 				f3 acc = mk3(0.f, 0.f, 0.f);
+				if (COUNT && uni(wt_w[wv].cm[6]))
+					sc.pclear += nl;
 				for (uint32_t base = 0; base < nl; base += WAVE) {
+					/* an all-clear point: its packets inside one emitter's samples in clear_run */
+					reread_barrier();
+					if (uni(wt_w[wv].cm[6])) {
+						base = clear_run<COUNT, WALK>(ks, rec, nl, base, acc, sc, wt_w[wv].cm);
+						if (base >= nl)
+							break;
+					}
 					const uint32_t idx = base + lane_id();
 					acc = add3(acc, light_sample<COUNT, WALK, true, LA>(ks, rec, 0u, idx, idx < nl, sc, top_q, top_e, stk, t8, wv,
 											    wt_w[wv].cm));
@@ -1445,6 +1673,9 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 			atomicAdd(&ctr[RTX_C_FARS], sc.far);
 			atomicAdd(&ctr[RTX_C_SSPILL], sc.spills);
 			atomicAdd(&ctr[RTX_C_SCLEAR], sc.clear);
+			atomicAdd(&ctr[RTX_C_SPSKIP], sc.pskip);
+			atomicAdd(&ctr[RTX_C_SLSKIP], sc.lskip);
+			atomicAdd(&ctr[RTX_C_SPCLEAR], sc.pclear);
 		}
 	}
 }
@@ -1477,6 +1708,52 @@ __global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in,
 	case RTX_KAT_SPEC_POW:
 		y[0] = fmaxf(0.f, sh_pow(x[0], x[1]));
 		break;
+	case RTX_KAT_PLANE_CLEAR:
+	case RTX_KAT_LIN_CLEAR: {
+		/* point_masks' predicates for one point, light and plane / record, beside the per-ray test of
+		 * one of k_shadow's own samples of that light */
+		const f3 p = ld3(x);
+		DEmitter e;
+		e.type = x[3] == 0.f ? RTX_SPHERE : RTX_TRIANGLE;
+		e.num_lights = 1;
+		for (int k = 0; k < 3; k++) {
+			e.p0[k] = x[4 + k];
+			e.p1[k] = x[7 + k];
+			e.p2[k] = x[10 + k];
+			e.li[k] = 1.f;
+		}
+		e.radius = x[13];
+		f3 lc, ldir, li;
+		float lr, ldist, dsq;
+		emitter_sphere(e, lc, lr);
+		const f3 ax0 = sub3(lc, p);
+		const float L = sqrtf(magsqr3(ax0));
+		const bool pk = kind == RTX_KAT_PLANE_CLEAR;
+		sample_ray(RTX_RNG_CONST, e, 0u, x[pk ? 19 : 26], x[pk ? 20 : 27], p, ldir, ldist, dsq, li);
+		bool clear, blocks;
+		if (pk) {
+			clear = plane_clear(ld3(x + 14), x[17], x[18], p, lc, lr, L);
+			blocks = plane_blocks(ld3(x + 14), x[17], p, ldir, x[18], ldist);
+		} else {
+			const bool sph = x[14] == 0.f;
+			float rs[4];
+			rtx_record_sphere(sph, x + 15, x + 18, x + 21, x[24], rs);
+			clear = L > 1.01f * lr && !cone_meets<true>(cone_of(p, lc, lr, ax0, L), p, make_float4(rs[0], rs[1], rs[2], rs[3]));
+			if (sph) {
+				float t = 0.f;
+				blocks = hit_sphere(ld3(x + 15), x[24], p, ldir, x[25], t) && t < ldist;
+			} else {
+				const f3 w0 = ld3(x + 15);
+				blocks = any_tri(w0, sub3(ld3(x + 18), w0), sub3(ld3(x + 21), w0), p, ldir, x[25], ldist);
+			}
+		}
+		y[0] = clear ? 1.f : 0.f;
+		y[1] = blocks ? 1.f : 0.f;
+		y[2] = ldir.x;
+		y[3] = ldir.y;
+		y[4] = ldir.z;
+		y[5] = ldist;
+	} break;
 	case RTX_KAT_BOX_Q: {
 		/* the walk's setup (shadow_query / shadow_walk) and its box test on the quantised box */
 		const f3 o = ld3(x), d = ld3(x + 3), qo = ld3(x + 12), qs = ld3(x + 15);
@@ -1728,6 +2005,7 @@ for (int a = 0; a < 3; a++) {
 	ka.cull = (const float4 *)S->cull;
 	ka.num_cull = (walk == WALK_W8 && S->cull) ? S->num_cull : 0u;
 	ka.cull_slots = S->cull_slots;
+	ka.point = S->point;
 	ka.num_lin = S->lin ? S->num_lin : 0u;
 	if (walk == WALK_W8) { /* the 8-wide tree's own frame; the emitters it leaves out are tested linearly */
 		for (int a = 0; a < 3; a++) {
@@ -1738,6 +2016,9 @@ for (int a = 0; a < 3; a++) {
 		ka.lin = S->emitters;
 		ka.num_lin = S->w8noemit ? S->num_emitters : 0u;
 	}
+	/* the listed records' bounding spheres, when they are those of the records this walk lists */
+	ka.lsph = (const float4 *)S->lsph;
+	ka.num_lsph = (S->lsph && S->num_lsph == ka.num_lin) ? S->num_lsph : 0u;
 	if (walk == WALK_W8)
 		return launch_walk<WALK_W8>(ka, nw, cus, count, stream);
 	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream);

@@ -203,6 +203,13 @@ def write_stl(path, tris):
     _check_scene(scene_lib().rtx_stl_write(os.fsencode(path), tris.shape[0], tris.ctypes.data))
 
 
+def _with_point_stats(s, p):
+    """the rtx_point_stats counters as attributes of the Stats beside them"""
+    for f, _ in abi.PointStats._fields_:
+        setattr(s, f, getattr(p, f))
+    return s
+
+
 class Renderer:
     """One rtx context on one HIP device (rtx_open .. rtx_close)."""
 
@@ -266,7 +273,9 @@ class Renderer:
     def stats(self):
         s = Stats()
         _check(self.lib.rtx_get_stats(self._ctx, C.byref(s)))
-        return s
+        p = abi.PointStats()
+        _check(self.lib.rtx_get_point_stats(self._ctx, C.byref(p)))
+        return _with_point_stats(s, p)
 
     def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
         """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
@@ -383,12 +392,16 @@ class Group:
     def stats(self):
         s = Stats()
         _check(self.lib.rtx_group_get_stats(self._g, C.byref(s)))
-        return s
+        p = abi.PointStats()
+        _check(self.lib.rtx_group_get_point_stats(self._g, C.byref(p)))
+        return _with_point_stats(s, p)
 
     def device_stats(self, r):
         s = Stats()
         _check(self.lib.rtx_group_device_stats(self._g, r, C.byref(s)))
-        return s
+        p = abi.PointStats()
+        _check(self.lib.rtx_group_device_point_stats(self._g, r, C.byref(p)))
+        return _with_point_stats(s, p)
 
     def member(self, r):
         """what the runtime reports about member r (rtx_group_member_info): its device, its RCCL

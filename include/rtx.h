@@ -239,6 +239,17 @@ typedef struct rtx_stats {
 	                                   * (RTX_OPT_SHADOW_CULL) */
 } rtx_stats;
 
+/* What a shade point's masks let skip (RTX_OPT_SHADOW_POINT), only with count_traversal: the
+ * continuation of rtx_stats, in a struct of its own so that rtx_stats keeps its size for callers
+ * built against it (rtx_get_point_stats, after the render like rtx_get_stats) */
+typedef struct rtx_point_stats {
+	uint64_t shadow_plane_skipped;    /* plane tests of shadow rays not run (shadow_plane_tests counts those run) */
+	uint64_t shadow_lin_skipped;      /* tests of objects taken one by one (the emitters out of the 8-wide tree,
+	                                   * RTX_WALK_LINEAR's objects) not run */
+	uint64_t shadow_point_clear;      /* shadow rays of all-clear shade points: nothing can block any of their
+	                                   * samples, so their packets run no shadow query at all */
+} rtx_point_stats;
+
 typedef struct rtx_ctx rtx_ctx;
 
 /* BVH builders for rtx_upload_scene (replacing accel_init, accel.c:266-315) */
@@ -264,6 +275,7 @@ int rtx_render(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, f
 int rtx_render_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, void *d_rgb, void *d_z,
 		      void *stream);
 int rtx_get_stats(const rtx_ctx *ctx, rtx_stats *out);
+int rtx_get_point_stats(const rtx_ctx *ctx, rtx_point_stats *out);
 /* Builder used by subsequent rtx_upload_scene calls on this context (RTX_BUILD_*). */
 int rtx_set_builder(rtx_ctx *ctx, int builder);
 
@@ -308,8 +320,13 @@ enum rtx_option {
 	                               * emitter (emitters 0..7); 0: every packet walks */
 	RTX_OPT_RAYS_GRAB = 12,       /* ray queries: 64-ray packets a wave takes per queue grab, 1..64 (0 = automatic,
 	                               * default: 1, up to 4 for batches of 16 packets per wave and more) */
-	RTX_OPT_RAYS_QUEUES = 13      /* ray queries: atomic packet queues the waves are dealt over, 1..8 (0 =
+	RTX_OPT_RAYS_QUEUES = 13,     /* ray queries: atomic packet queues the waves are dealt over, 1..8 (0 =
 	                               * automatic, default: 8); any value gives the same hits */
+	RTX_OPT_SHADOW_POINT = 14     /* 1 (default): a shade point with 64 light samples or more decides once, per
+	                               * emitter, that no sample's ray can meet a plane or an object k_shadow tests
+	                               * one by one; its packets then skip those tests, and a point clear of
+	                               * everything runs a loop with no shadow query (same image); 0: every packet
+	                               * tests them.  RTX_OPT_SHADOW_CULL 0 turns this off too */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -419,6 +436,9 @@ int rtx_group_render(rtx_group *g, const rtx_frame *frame, const rtx_params *par
 int rtx_group_get_stats(const rtx_group *g, rtx_stats *out);
 /* the statistics of device r (0 <= r < rtx_group_size) for the last frame */
 int rtx_group_device_stats(const rtx_group *g, int r, rtx_stats *out);
+/* rtx_point_stats of the last group render: summed over the devices, and device r's own */
+int rtx_group_get_point_stats(const rtx_group *g, rtx_point_stats *out);
+int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point_stats *out);
 /* What the runtime reports about member r, read back rather than assumed (a line that claims N
  * devices can show that N communicators of one clique formed on N distinct devices) */
 typedef struct rtx_group_member {

@@ -29,6 +29,15 @@
  *                    (the box quantised to 16 bits as for KAT_BOX_Q, then to 8 bits in an 8-wide node frame of
  *                     origin org (grid units, <= the 16-bit lo) and steps 2^e, rtx_quant.h rtx_quantise8, and
  *                     tested by the 8-wide walk's child test, rtx_shadow.hip w8_child)
+ * -- k_shadow's per-point masks (rtx_shadow.hip point_masks) against the per-ray tests they stand for --
+ * KAT_PLANE_CLEAR(17) P3 etype v0_3 v1_3 v2_3 r n3 dd eps u1 u2 = 21   clear blocks d3 dist      = 6
+ *                    (etype 0: a sphere light of centre v0 and radius r; 1: the triangle light v0 v1 v2.  clear:
+ *                     plane_clear for the light's padded bounding sphere; blocks: plane_blocks of the shadow ray
+ *                     from P to the light point of (u1, u2), k_shadow's own sample; d dist: that ray's direction and length)
+ * KAT_LIN_CLEAR(18)  P3 etype v0_3 v1_3 v2_3 r rtype w0_3 w1_3 w2_3 rr reps u1 u2 = 28  clear blocks d3 dist = 6
+ *                    (the listed record: rtype 0 the sphere (w0, rr), 1 the triangle w0 w1 w2, epsilon reps; clear:
+ *                     the cone from P around the light misses the record's padded bounding sphere, formed as at
+ *                     upload (rtx_quant.h rtx_record_sphere); blocks: the record's shadow test of that sample's ray)
  * Texture records use the params' u32conv for the float->uint32 conversion.
  */
 #ifndef RTX_KAT_H
@@ -52,11 +61,13 @@ enum rtx_kat_kind {
 	RTX_KAT_BOX_Q = 14,
 	RTX_KAT_SPEC_POW = 15,
 	RTX_KAT_BOX_Q8 = 16,
-	RTX_KAT_NKINDS = 17,
+	RTX_KAT_PLANE_CLEAR = 17,
+	RTX_KAT_LIN_CLEAR = 18,
+	RTX_KAT_NKINDS = 19,
 };
 #define RTX_KAT_FIRST_SHADOW RTX_KAT_ANY_TRI /* kinds >= this run in rtx_shadow.hip */
 
-static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25 };
-static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2 };
+static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28 };
+static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6 };
 
 #endif

@@ -63,14 +63,24 @@ RTX_HD uint32_t rtx_hash32(uint32_t x)
 
 /* two uniform floats in [0,1).  The (key, stream) part is one splitmix64 round, the same for every
  * index, so a wave whose lanes share the key and the stream (the 64 light samples of one shade
- * point) computes it once in scalar registers; each index then costs two 32-bit hashes. */
-RTX_HD void rtx_draw2(uint64_t key, uint32_t stream, uint32_t index, float *u1, float *u2)
+ * point) computes it once in scalar registers (rtx_draw_mix); each index then costs two 32-bit
+ * hashes (rtx_draw2_mixed). */
+RTX_HD uint64_t rtx_draw_mix(uint64_t key, uint32_t stream)
 {
-	const uint64_t s = rtx_mix64(key ^ ((uint64_t)stream + 1u) * 0xd1b54a32d192ed03ull);
+	return rtx_mix64(key ^ ((uint64_t)stream + 1u) * 0xd1b54a32d192ed03ull);
+}
+
+RTX_HD void rtx_draw2_mixed(uint64_t s, uint32_t index, float *u1, float *u2)
+{
 	const uint32_t a = rtx_hash32((uint32_t)s ^ index);
 	const uint32_t b = rtx_hash32((uint32_t)(s >> 32) ^ a);
 	*u1 = (float)(a >> 8) * (1.0f / 16777216.0f);
 	*u2 = (float)(b >> 8) * (1.0f / 16777216.0f);
+}
+
+RTX_HD void rtx_draw2(uint64_t key, uint32_t stream, uint32_t index, float *u1, float *u2)
+{
+	rtx_draw2_mixed(rtx_draw_mix(key, stream), index, u1, u2);
 }
 
 #endif
