@@ -353,7 +353,9 @@ int rtx_read_wide_tree(rtx_ctx *ctx, void *entries, uint32_t capacity, uint32_t 
  */
 typedef struct rtx_ray {          /* 32 B */
 	float origin[3];
-	float tmax;               /* hits need t < tmax; INFINITY (or NaN) = unbounded, as the renderer's rays */
+	float tmax;               /* hits need t < tmax, strictly: tmax = a hit's own t excludes it, the next float above
+	                           * keeps it; INFINITY (or NaN) = unbounded, as the renderer's rays; 0, a negative
+	                           * value or -INFINITY = no hit (every t lies above its object's epsilon) */
 	float dir[3];             /* unit length (the caller's duty: t is in units of |dir|); a NaN component =
 	                           * miss, as cast_ray's total-internal-reflection rays */
 	uint32_t pad_;

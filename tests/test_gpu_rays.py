@@ -12,27 +12,18 @@ import pytest
 
 import rays_frames as RF
 import rtxpy
+from rays_exhaustive import objects_of
 from rtxpy import abi
 
 pytestmark = pytest.mark.gpu
 
 W, H, N = RF.W, RF.H, RF.W * RF.H
-OBJ_DTYPE = np.dtype([("type", "<i4"), ("material", "<i4"), ("num_lights", "<u4"), ("epsilon", "<f4"), ("p0", "<f4", 3),
-                      ("p1", "<f4", 3), ("p2", "<f4", 3), ("e1", "<f4", 3), ("e2", "<f4", 3), ("n", "<f4", 3),
-                      ("radius", "<f4"), ("d", "<f4")])
 SENTINEL = 123456.0
 
 
 def as_hits(t):
     """a torch (n, 8) float32 device tensor of rtx_hit records as a numpy structured array"""
     return t.cpu().numpy().view(abi.HIT_DTYPE).reshape(-1)
-
-
-def objects_of(scene):
-    assert OBJ_DTYPE.itemsize == ctypes.sizeof(abi.Object)
-    n = scene.desc.num_objects
-    raw = np.ctypeslib.as_array(ctypes.cast(scene.desc.objects, ctypes.POINTER(ctypes.c_uint8)), shape=(n * OBJ_DTYPE.itemsize,))
-    return raw.view(OBJ_DTYPE)
 
 
 class World:
