@@ -857,6 +857,31 @@ static int build_lsph(rtx_ctx *c, const std::vector<DEmitter> &recs, uint32_t *n
 	return RTX_OK;
 }
 
+/* k_shadow's dark samples (DScene.dark_ok, RTX_OPT_SHADOW_DARK): a sample whose terms are 0 may skip
+ * its shadow query only if nothing the query gathers could turn 0 into NaN or let a product grow,
+ * so every transmittance a shadow ray can meet (the materials' kt, which the plane and emitter
+ * records copy) is finite with |kt| <= 1 and every emitter's intensity is finite */
+static bool scene_dark_ok(const HostScene &hs)
+{
+	for (const DMaterial &m : hs.mats)
+		for (int k = 0; k < 3; k++)
+			if (!(std::fabs(m.kt[k]) <= 1.f))
+				return false;
+	for (const DPlane &p : hs.planes)
+		for (int k = 0; k < 3; k++)
+			if (!(std::fabs(p.kt[k]) <= 1.f))
+				return false;
+	for (const DEmitter &e : hs.emit)
+		for (int k = 0; k < 3; k++)
+			if (!std::isfinite(e.li[k]) || !(std::fabs(e.kt[k]) <= 1.f))
+				return false;
+	for (const DEmitter &e : hs.lin)
+		for (int k = 0; k < 3; k++)
+			if (!(std::fabs(e.kt[k]) <= 1.f))
+				return false;
+	return true;
+}
+
 int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 {
 	int rc;
@@ -964,6 +989,7 @@ int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 	S.num_cull = ncull;
 	S.lsph = nlsph ? (const float *)c->d_lsph : nullptr;
 	S.num_lsph = nlsph;
+	S.dark_ok = scene_dark_ok(hs) ? 1u : 0u;
 	c->total_lights = 0;
 	for (const DEmitter &e : hs.emit)
 		c->total_lights += e.num_lights;
@@ -1205,6 +1231,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 			Ssh.num_cull = 0;
 		Ssh.cull_slots = c->opt_cull == 2 ? 1u : 0u;
 		Ssh.point = (c->opt_cull && c->opt_point) ? 1u : 0u; /* RTX_OPT_SHADOW_POINT */
+		Ssh.dark = (c->opt_cull && c->opt_dark) ? 1u : 0u;   /* RTX_OPT_SHADOW_DARK */
 		HIP_TRY(rtx_launch_shadow(&Ssh, &P, c->d_sp, perm, n_sp, per_wave, slot_b, c->d_contrib, c->d_ctr,
 					  p->count_traversal, (uint32_t)c->cus, stream));
 		HIP_TRY(hipEventRecord(c->ev[2], stream));
@@ -1259,6 +1286,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	c->pstats.shadow_plane_skipped = ctr[RTX_C_SPSKIP];
 	c->pstats.shadow_lin_skipped = ctr[RTX_C_SLSKIP];
 	c->pstats.shadow_point_clear = ctr[RTX_C_SPCLEAR];
+	c->dstats.shadow_dark_rays = ctr[RTX_C_SDARK];
+	c->dstats.shadow_dark_packet_rays = ctr[RTX_C_SDARKPK];
 	st.node_visits = ctr[RTX_C_NODES] + st.shadow_node_visits;
 	st.tri_tests = ctr[RTX_C_TRIS] + ctr[RTX_C_STRIS];
 	st.sphere_tests = ctr[RTX_C_SPHERES] + ctr[RTX_C_SSPHERES];
@@ -1630,6 +1659,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow point masks %lld is not 0 or 1", (long long)value);
 		c->opt_point = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_DARK:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow dark samples %lld is not 0 or 1", (long long)value);
+		c->opt_dark = (int)value;
+		return RTX_OK;
 	}
 	return fail(RTX_ERR_ARG, "unknown option %d", option);
 }
@@ -1666,6 +1700,14 @@ extern "C" int rtx_get_point_stats(const rtx_ctx *c, rtx_point_stats *out)
 	if (!c || !out)
 		return fail(RTX_ERR_ARG, "null argument");
 	*out = c->pstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_get_dark_stats(const rtx_ctx *c, rtx_dark_stats *out)
+{
+	if (!c || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = c->dstats;
 	return RTX_OK;
 }
 

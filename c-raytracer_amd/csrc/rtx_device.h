@@ -266,6 +266,10 @@ typedef struct DScene {
 	uint32_t num_lsph;
 	uint32_t point;        /* RTX_OPT_SHADOW_POINT (and RTX_OPT_SHADOW_CULL not 0): planes and listed records are
 	                        * decided once per shade point of the wave-uniform path */
+	uint32_t dark_ok;      /* every material's kt and every emitter's li is finite and |kt| <= 1 (set at upload):
+	                        * a light sample whose terms are 0 stays 0 under any transmittance a walk gathers */
+	uint32_t dark;         /* RTX_OPT_SHADOW_DARK (and RTX_OPT_SHADOW_CULL not 0): such samples skip their shadow
+	                        * query on the wave-uniform path (rtx_shadow.hip sample_dark) */
 } DScene;
 #define RTX_CULL_MAX 64
 
@@ -338,6 +342,9 @@ enum {
 	RTX_C_SPSKIP,       /* count mode: plane tests a shade point's plane mask let skip */
 	RTX_C_SLSKIP,       /* count mode: listed-object tests its listed-object mask let skip */
 	RTX_C_SPCLEAR,      /* count mode: shadow rays of all-clear shade points (clear_run) */
+	RTX_C_SDARK,        /* count mode: dark shadow rays answered without a query (sample_dark; packets the cone
+	                     * cull cleared are not looked at) */
+	RTX_C_SDARKPK,      /* count mode: ... of which in packets of dark rays alone */
 	RTX_C_N
 };
 

@@ -66,6 +66,7 @@ struct rtx_group {
 	std::vector<size_t> recv_cap;  /* capacity of d_recv[r] in records */
 	rtx_stats stats{};
 	rtx_point_stats pstats{};
+	rtx_dark_stats dstats{};
 };
 
 extern "C" void rtx_group_close(rtx_group *g)
@@ -498,6 +499,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	/* statistics: counts summed, times of the slowest device */
 	rtx_stats s = c0->stats;
 	rtx_point_stats ps = c0->pstats;
+	rtx_dark_stats ds = c0->dstats;
 	for (int r = 1; r < n; r++) {
 		const rtx_stats &o = g->ctx[r]->stats;
 		s.closest_rays += o.closest_rays;
@@ -524,6 +526,8 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 		ps.shadow_plane_skipped += g->ctx[r]->pstats.shadow_plane_skipped;
 		ps.shadow_lin_skipped += g->ctx[r]->pstats.shadow_lin_skipped;
 		ps.shadow_point_clear += g->ctx[r]->pstats.shadow_point_clear;
+		ds.shadow_dark_rays += g->ctx[r]->dstats.shadow_dark_rays;
+		ds.shadow_dark_packet_rays += g->ctx[r]->dstats.shadow_dark_packet_rays;
 		s.waves += o.waves;
 		s.chunks += o.chunks;
 		s.kernel_ms = std::max(s.kernel_ms, o.kernel_ms);
@@ -538,6 +542,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	s.devices = (uint32_t)n;
 	g->stats = s;
 	g->pstats = ps;
+	g->dstats = ds;
 	return RTX_OK;
 }
 
@@ -564,6 +569,24 @@ extern "C" int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point
 	if (r < 0 || r >= g->n)
 		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
 	*out = g->ctx[r]->pstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_get_dark_stats(const rtx_group *g, rtx_dark_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = g->dstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (r < 0 || r >= g->n)
+		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
+	*out = g->ctx[r]->dstats;
 	return RTX_OK;
 }
 

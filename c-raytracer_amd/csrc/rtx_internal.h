@@ -122,6 +122,7 @@ struct rtx_ctx {
 	size_t fb_pixels = 0;
 	rtx_stats stats{};
 	rtx_point_stats pstats{}; /* rtx_get_point_stats */
+	rtx_dark_stats dstats{};  /* rtx_get_dark_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
 	unsigned long long *d_rctr = nullptr;
 	void *d_qrays = nullptr, *d_qhits = nullptr;
@@ -142,6 +143,7 @@ struct rtx_ctx {
 	uint32_t opt_rays_queues = 0; /* RTX_OPT_RAYS_QUEUES: k_rays packet queues (0: automatic) */
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
 	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
+	int opt_dark = 1;         /* RTX_OPT_SHADOW_DARK: light samples that add nothing skip their shadow query */
 	uint32_t mem_share = 1;   /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */
 };

@@ -166,6 +166,8 @@ struct ShadowCount {
 	u64 pskip;     /* plane tests the point's plane mask let skip (point_masks) */
 	u64 lskip;     /* listed-object tests its listed-object mask let skip */
 	u64 pclear;    /* rays of all-clear points (clear_run) */
+	u64 dark;      /* rays answered without a query: their sample adds nothing to the point (sample_dark) */
+	u64 dpack;     /* ... of which in packets whose every sample was dark (no shadow query at all) */
 };
 
 /* one primitive record (a, b, c = its first 48 bytes) against this lane's shadow ray
@@ -810,6 +812,7 @@ const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi
 	const float4 *lsph;   /* DScene.lsph: the bounding spheres of the `lin` records (point_masks) */
 	uint32_t num_lsph;    /* num_lin when they are there, else 0 */
 	uint32_t point;       /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
+	uint32_t dark;        /* RTX_OPT_SHADOW_DARK (and the scene allows it, DScene.dark_ok): dark samples skip their query */
 };
 
 __device__ __forceinline__ void reread_barrier() { asm volatile("" ::: "memory"); }
@@ -889,31 +892,75 @@ __device__ __forceinline__ float sample_att(const KShadow &ks, float ldist, floa
 	return sample_att_of((int32_t)uni((uint32_t)ks.attenuation), ks.att_offset, ldist, dsq);
 }
 
-/* direct-lighting terms of one unblocked light sample (render.c:199-228) from the shade point's
- * normal n, view direction dir, diffuse colour kd and its material's ks3 / shin */
-__device__ __forceinline__ f3 shade_terms(int32_t att, int32_t refl, f3 n, f3 dir, f3 kd, f3 ks3, float shin, f3 ldir, f3 li, float attf)
+/* The two factors of a light sample's terms (render.c:202-226): pd = fmaxf(0, ldir.n) of the
+ * diffuse term and pw = fmaxf(0, powf(specular_mul, shininess)) of the specular one.  shade_terms
+ * and dark_terms both take them from here, so the two cannot disagree. */
+__device__ __forceinline__ float shade_pd(f3 n, f3 ldir, float &a)
 {
-	const float a = dot3(ldir, n);
-	if (att != RTX_ATT_NONE)
-		li = mul3s(li, attf);
-	const f3 diff = mul3s(mul3v(kd, li), fmaxf(0.f, a));
+	a = dot3(ldir, n);
+	return fmaxf(0.f, a);
+}
+__device__ __forceinline__ float shade_pw(int32_t refl, f3 n, f3 dir, float shin, f3 ldir, float a)
+{
 	float sm;
 	if (refl == RTX_BLINN)
 		sm = -dot3(n, norm3(add3(mul3s(ldir, -1.f), dir)));
 	else
 		sm = -dot3(sub3(mul3s(n, 2.f * a), ldir), dir);
-	const f3 spec = mul3s(mul3v(ks3, li), fmaxf(0.f, sh_pow(sm, shin)));
+	return fmaxf(0.f, sh_pow(sm, shin));
+}
+
+/* direct-lighting terms of one unblocked light sample (render.c:199-228) from the shade point's
+ * normal n, view direction dir, diffuse colour kd and its material's ks3 / shin */
+__device__ __forceinline__ f3 shade_terms(int32_t att, int32_t refl, f3 n, f3 dir, f3 kd, f3 ks3, float shin, f3 ldir, f3 li, float attf)
+{
+	float a;
+	const float pd = shade_pd(n, ldir, a);
+	if (att != RTX_ATT_NONE)
+		li = mul3s(li, attf);
+	const f3 diff = mul3s(mul3v(kd, li), pd);
+	const f3 spec = mul3s(mul3v(ks3, li), shade_pw(refl, n, dir, shin, ldir, a));
 	return add3(diff, spec);
 }
 
-/* the same of the shade point `rec`, read after the walk */
+/* A dark sample (RTX_OPT_SHADOW_DARK): shade_terms gives +-0 in every channel for this sample's li
+ * and for li times any product of transmittances |kt| <= 1, so the sample adds nothing to its
+ * point whether or not it is blocked (acc + (+-0) == acc bit for bit, what a blocked sample
+ * leaves), and its shadow query need not run.  That is: a light behind the surface (pd == 0) or
+ * a point without diffuse colour, and a specular factor of 0 (pw == 0: ks aside, specular_mul
+ * <= 0 under an odd or non-integer shininess) or a material without ks.  The products must stay
+ * finite, or a 0 factor would give NaN, not 0: kd li' and ks li' (li' = li attf) are finite
+ * here, and with a transmittance T, |T| <= 1 (the scene's flag, rtx_api.cpp scene_dark_ok),
+ * |fl(fl(li T) attf)| <= |fl(li attf)| as rounding is monotonic, so the products formed after
+ * a walk are no larger.  The lanes' pw is formed only when some lane passed the diffuse part
+ * (a lit point's packets pay the dot product alone).  (KAT: RTX_KAT_DARK) */
+__device__ __forceinline__ bool fin1(float x) { return fabsf(x) < __builtin_inff(); }
+__device__ __forceinline__ bool fin3(f3 v) { return fin1(v.x) && fin1(v.y) && fin1(v.z); }
+__device__ __forceinline__ bool zero3(f3 v) { return v.x == 0.f && v.y == 0.f && v.z == 0.f; }
+__device__ __forceinline__ bool dark_terms(int32_t att, int32_t refl, f3 n, f3 dir, f3 kd, f3 ks3, float shin, f3 ldir, f3 li, float attf,
+					   bool act)
+{
+	float a;
+	const float pd = shade_pd(n, ldir, a);
+	if (att != RTX_ATT_NONE)
+		li = mul3s(li, attf);
+	const bool fin = fin1(attf) && fin3(mul3v(kd, li)) && fin3(mul3v(ks3, li));
+	const bool dk = act && fin && (pd == 0.f || (zero3(kd) && fin1(pd)));
+	if (!ballot(dk))
+		return false;
+	const float pw = shade_pw(refl, n, dir, shin, ldir, a);
+	return dk && (pw == 0.f || (zero3(ks3) && fin1(pw)));
+}
+
+/* the shading inputs of the shade point `rec`: normal, view direction, diffuse colour and its
+ * material's ks / shininess (UNI: a wave-uniform record and its material through scalar reads) */
 template <bool UNI>
-__device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, f3 ldir, f3 li, float attf)
+__device__ __forceinline__ void point_shading(const KShadow &ks, const float4 *rec, f3 &n, f3 &dir, f3 &kd, f3 &ks3, float &shin)
 {
 	const float4 q1 = sp_field<UNI>(rec, 1), q2 = sp_field<UNI>(rec, 2), q3 = sp_field<UNI>(rec, 3);
-	const f3 n = mk3(q1.x, q1.y, q1.z), dir = mk3(q2.x, q2.y, q2.z);
-	f3 ks3;
-	float shin;
+	n = mk3(q1.x, q1.y, q1.z);
+	dir = mk3(q2.x, q2.y, q2.z);
+	kd = mk3(q3.x, q3.y, q3.z);
 	if (UNI) { /* the material of a wave-uniform record: scalar reads */
 		const auto &m = cptr(unip(ks.mats))[__float_as_uint(q3.w)];
 		ks3 = mk3(m.ks[0], m.ks[1], m.ks[2]);
@@ -923,8 +970,28 @@ __device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, 
 		ks3 = ld3(m.ks);
 		shin = m.shininess;
 	}
-	return shade_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, mk3(q3.x, q3.y, q3.z), ks3,
-			   shin, ldir, li, attf);
+}
+
+/* shade_terms of the shade point `rec`, read after the walk */
+template <bool UNI>
+__device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, f3 ldir, f3 li, float attf)
+{
+	f3 n, dir, kd, ks3;
+	float shin;
+	point_shading<UNI>(ks, rec, n, dir, kd, ks3, shin);
+	return shade_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, kd, ks3, shin, ldir, li,
+			   attf);
+}
+
+/* dark_terms of the shade point `rec`, read before the walk (nothing of it lives across it) */
+template <bool UNI>
+__device__ __forceinline__ bool sample_dark(const KShadow &ks, const float4 *rec, f3 ldir, f3 li, float attf, bool act)
+{
+	f3 n, dir, kd, ks3;
+	float shin;
+	point_shading<UNI>(ks, rec, n, dir, kd, ks3, shin);
+	return dark_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, kd, ks3, shin, ldir, li,
+			  attf, act);
 }
 
 /* the light point of sample j of emitter E from its draws u1, u2 (object.c:293-304, 403-419:
@@ -1210,7 +1277,7 @@ __device__ __forceinline__ void count_skips(const KShadow &ks, uint32_t na, uint
 /* one light sample per lane of the shade point `rec` (render.c:170-229): the light point of
  * sample idx (emitters in scene order, the hit object skipped), its shadow ray, attenuation
  * and Phong / Blinn.  Argument-block fields are read from LDS behind reread barriers. */
-template <bool COUNT, int WALK, bool UNI, bool LA, bool SC = false>
+template <bool COUNT, int WALK, bool UNI, bool LA, bool SC = false, bool DK = false>
 __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_uni, uint32_t sidv, uint32_t idx, bool act, ShadowCount &sc,
 					   const uint4 *top_q, const uint32_t *top_e, lds_u32 *stk, const uint4 *t8, uint32_t wv,
 					   const uint32_t *cmask, uint32_t lclr = 0u)
@@ -1272,15 +1339,32 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 		clear = ballot(act) && !ballot(act && !lc);
 	}
 	const float attf = sample_att(ks, ldist, dsq);
+	/* the wave-uniform path's dark samples (sample_dark) take no part in the query: their lanes
+	 * enter it as idle ones, and a packet of dark samples alone runs neither loop nor walk.  A
+	 * packet the cone cull cleared has no walk to save: its samples are not looked at */
+	bool qry = act;
+	bool none = false;
+	if (UNI && DK && uni(ks.dark) && !far && !clear) {
+		qry = act && !sample_dark<UNI && RTX_SH_SPUNI>(ks, rec, ldir, li, attf, act);
+		none = !ballot(qry);
+	}
 	const QBvh Q = make_qbvh<WALK>(ks, top_q, top_e, stk, t8, wv);
-	const bool have_tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK && !clear;
+	const bool have_tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK && !clear && !none;
 	if (COUNT && clear)
 		sc.clear += (u64)popc64(ballot(act));
-	if (COUNT && UNI)
+	if (COUNT && UNI) {
 		count_skips(ks, popc64(ballot(act)), eobj, pclr, rclr, sc);
+		/* the dark rays of packets the cone cull had not cleared; shadow_plane_tests keeps counting
+		 * the plane tests of every ray the plane mask did not clear, dark ones included */
+		const uint32_t nd = popc64(ballot(act && !qry));
+		sc.dark += nd;
+		if (none)
+			sc.dpack += nd;
+		sc.pln += (u64)nd * (pclr ? 0u : uni(ks.num_planes));
+	}
 	const bool blocked = shadow_query<COUNT, WALK, LA>(Q, unip(ks.recs), unip(ks.mats), unip(ks.planes),
-							 (UNI && pclr) ? 0u : uni(ks.num_planes), unip(ks.lin),
-							 (UNI && rclr) ? 0u : uni(ks.num_lin), have_tree, ks.tf, act, far != 0, p, ldir,
+							 (UNI && (pclr || none)) ? 0u : uni(ks.num_planes), unip(ks.lin),
+							 (UNI && (rclr || none)) ? 0u : uni(ks.num_lin), have_tree, ks.tf, qry, far != 0, p, ldir,
 							 ldist, eobj, li, sc);
 	reread_barrier();
 	if (!UNI && RTX_SH_RECAFTER) {
@@ -1288,7 +1372,7 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 		rec = unip(ks.sp) + (size_t)sidv * SPREC;
 	}
 	f3 contribution = mk3(0.f, 0.f, 0.f);
-	if (act && !blocked)
+	if (qry && !blocked)
 		contribution = shade_light<UNI && RTX_SH_SPUNI>(ks, rec, ldir, li, attf);
 	return contribution;
 }
@@ -1371,7 +1455,8 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
  * (RTX_C_SPQUEUE), in processing (Morton) order, until the points run out. */
 /* PATH: 0 both packet layouts (a runtime branch on slot_b: the counting instances), 1 only the
  * wave-uniform packets (slot_b = 64), 2 only the lane slots (slot_b < 64), 3 the lane slots with
- * their cone cull (RTX_OPT_SHADOW_CULL 2).  The product launches a
+ * their cone cull (RTX_OPT_SHADOW_CULL 2), 4 the wave-uniform packets with their dark samples left
+ * out of the query (RTX_OPT_SHADOW_DARK).  The product launches a
  * kernel of one layout, so each gets a register allocation of its own: with both in one kernel a
  * change to the slot loop moved the uniform loop's spills into its walk */
 template <bool COUNT, int OCC, int WALK, int PATH>
@@ -1419,13 +1504,18 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 	/* the lane-stack addresses: per lane, or formed from lane_id() at each access (RTX_W8_LANEADDR; 2:
 	 * the lane-slot kernel only, whose allocation spilled the per-lane address and reloaded it at
 	 * every push and pop) */
-	constexpr bool LA = RTX_W8_LANEADDR == 2 ? PATH >= 2 : RTX_W8_LANEADDR != 0;
+	constexpr bool LA = RTX_W8_LANEADDR == 2 ? (PATH == 2 || PATH == 3) : RTX_W8_LANEADDR != 0;
 	/* the lane-slot path's cone cull (RTX_OPT_SHADOW_CULL 2) lives in its own instance, PATH 3, so
 	 * the default lane-slot kernel keeps its register allocation (with the code present but off,
 	 * scene6's k_shadow took 1083.4 against 1074.8 ms) */
 	constexpr bool SC = RTX_SH_SLOTCULL && WALK == WALK_W8 && (PATH == 3 || PATH == 0);
+	/* the dark samples (RTX_OPT_SHADOW_DARK) live in an instance of their own too, PATH 4: PATH 1 with
+	 * sample_dark, launched where the option is on and the scene walks a tree.  A scene without a
+	 * tree keeps PATH 1 as it was (with the code present but off, scene3's k_shadow took 52.7
+	 * against 52.4 ms) */
+	constexpr bool DK = PATH == 4 || PATH == 0;
 	lds_u32 *stk = (lds_u32 *)&wstk[wv][0][LA ? 0u : lane_id()];
-	ShadowCount sc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	ShadowCount sc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 	u64 rays_total = 0;
 	for (;;) {
 		reread_barrier();
@@ -1454,7 +1544,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 		if (lane_id() == 0)
 			off[WAVE] = total;
 		lds_sync();
-		if (PATH == 1 || (PATH == 0 && uni(ks.slot_b) == WAVE)) {
+		if (PATH == 1 || PATH == 4 || (PATH == 0 && uni(ks.slot_b) == WAVE)) {
 			/* >= 64 lights: every packet is 64 samples of ONE shade point.  The point is wave-uniform
 			 * (its record is read once per packet through one address, no owner search), each lane
 			 * sums its samples over the point's packets, and one butterfly per point reduces them. */
@@ -1502,7 +1592,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 							break;
 					}
 					const uint32_t idx = base + lane_id();
-					acc = add3(acc, light_sample<COUNT, WALK, true, LA>(ks, rec, 0u, idx, idx < nl, sc, top_q, top_e, stk, t8, wv,
+					acc = add3(acc, light_sample<COUNT, WALK, true, LA, false, DK>(ks, rec, 0u, idx, idx < nl, sc, top_q, top_e, stk, t8, wv,
 											    wt_w[wv].cm));
 				}
 				const float sx = wave_sum(acc.x), sy = wave_sum(acc.y), sz = wave_sum(acc.z);
@@ -1676,6 +1766,8 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 			atomicAdd(&ctr[RTX_C_SPSKIP], sc.pskip);
 			atomicAdd(&ctr[RTX_C_SLSKIP], sc.lskip);
 			atomicAdd(&ctr[RTX_C_SPCLEAR], sc.pclear);
+			atomicAdd(&ctr[RTX_C_SDARK], sc.dark);
+			atomicAdd(&ctr[RTX_C_SDARKPK], sc.dpack);
 		}
 	}
 }
@@ -1753,6 +1845,25 @@ __global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in,
 		y[3] = ldir.y;
 		y[4] = ldir.z;
 		y[5] = ldist;
+	} break;
+	case RTX_KAT_DARK: {
+		/* dark_terms beside shade_terms for the sample's li and for li through one transparent
+		 * surface, the attenuation factor formed as light_sample forms it */
+		const f3 n = ld3(x), dir = ld3(x + 3), kd = ld3(x + 6), ks3 = ld3(x + 9), ldir = ld3(x + 13), li = ld3(x + 17), kt = ld3(x + 23);
+		const float shin = x[12], ldist = x[16];
+		const int32_t att = (int32_t)x[20], refl = (int32_t)x[22];
+		const float attf = sample_att_of(att, x[21], ldist, ldist * ldist);
+		const bool ok = fin3(li) && fabsf(kt.x) <= 1.f && fabsf(kt.y) <= 1.f && fabsf(kt.z) <= 1.f; /* scene_dark_ok */
+		const bool dark = ok && dark_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf, true);
+		const f3 t0 = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf);
+		const f3 t1 = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, mul3v(li, kt), attf);
+		y[0] = dark ? 1.f : 0.f;
+		y[1] = t0.x;
+		y[2] = t0.y;
+		y[3] = t0.z;
+		y[4] = t1.x;
+		y[5] = t1.y;
+		y[6] = t1.z;
 	} break;
 	case RTX_KAT_BOX_Q: {
 		/* the walk's setup (shadow_query / shadow_walk) and its box test on the quantised box */
@@ -1891,7 +2002,7 @@ template <bool C, int O, int W> static hipError_t launch_shadow(const KShadow &k
 		return launch_shadow_p<C, O, W, 0>(ka, nw, cus, stream);
 	} else {
 		if (ka.slot_b == WAVE)
-			return launch_shadow_p<C, O, W, 1>(ka, nw, cus, stream);
+			return ka.dark ? launch_shadow_p<C, O, W, 4>(ka, nw, cus, stream) : launch_shadow_p<C, O, W, 1>(ka, nw, cus, stream);
 		if (W == WALK_W8 && ka.cull_slots && ka.num_cull)
 			return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 3>(ka, nw, cus, stream);
 		return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 2>(ka, nw, cus, stream);
@@ -1919,6 +2030,11 @@ extern "C" hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes)
 {
 	uint32_t a = 0, b = 0, a2 = 0;
 	hipError_t e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 1>(cus, &a);
+	if (e == hipSuccess) {
+		uint32_t a4 = 0;
+		e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 4>(cus, &a4);
+		a = a > a4 ? a : a4;
+	}
 	if (e == hipSuccess)
 		e = shadow_slots<false, RTX_SHADOW_OCC_SLOT, WALK_W8, 2>(cus, &a2);
 	if (e == hipSuccess) {
@@ -2006,6 +2122,9 @@ for (int a = 0; a < 3; a++) {
 	ka.num_cull = (walk == WALK_W8 && S->cull) ? S->num_cull : 0u;
 	ka.cull_slots = S->cull_slots;
 	ka.point = S->point;
+	/* only where shadow rays walk a tree: against a handful of listed objects the predicate costs
+	 * more than the tests it saves (scene3, RTX_WALK_LINEAR: 59.9 -> 61.7 ms per frame with it) */
+	ka.dark = (S->dark && S->dark_ok && ka.have_tree) ? 1u : 0u;
 	ka.num_lin = S->lin ? S->num_lin : 0u;
 	if (walk == WALK_W8) { /* the 8-wide tree's own frame; the emitters it leaves out are tested linearly */
 		for (int a = 0; a < 3; a++) {

@@ -203,10 +203,13 @@ def write_stl(path, tris):
     _check_scene(scene_lib().rtx_stl_write(os.fsencode(path), tris.shape[0], tris.ctypes.data))
 
 
-def _with_point_stats(s, p):
-    """the rtx_point_stats counters as attributes of the Stats beside them"""
+def _with_point_stats(s, p, d=None):
+    """the rtx_point_stats (and rtx_dark_stats) counters as attributes of the Stats beside them"""
     for f, _ in abi.PointStats._fields_:
         setattr(s, f, getattr(p, f))
+    if d is not None:
+        for f, _ in abi.DarkStats._fields_:
+            setattr(s, f, getattr(d, f))
     return s
 
 
@@ -275,7 +278,9 @@ class Renderer:
         _check(self.lib.rtx_get_stats(self._ctx, C.byref(s)))
         p = abi.PointStats()
         _check(self.lib.rtx_get_point_stats(self._ctx, C.byref(p)))
-        return _with_point_stats(s, p)
+        d = abi.DarkStats()
+        _check(self.lib.rtx_get_dark_stats(self._ctx, C.byref(d)))
+        return _with_point_stats(s, p, d)
 
     def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
         """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
@@ -394,14 +399,18 @@ class Group:
         _check(self.lib.rtx_group_get_stats(self._g, C.byref(s)))
         p = abi.PointStats()
         _check(self.lib.rtx_group_get_point_stats(self._g, C.byref(p)))
-        return _with_point_stats(s, p)
+        d = abi.DarkStats()
+        _check(self.lib.rtx_group_get_dark_stats(self._g, C.byref(d)))
+        return _with_point_stats(s, p, d)
 
     def device_stats(self, r):
         s = Stats()
         _check(self.lib.rtx_group_device_stats(self._g, r, C.byref(s)))
         p = abi.PointStats()
         _check(self.lib.rtx_group_device_point_stats(self._g, r, C.byref(p)))
-        return _with_point_stats(s, p)
+        d = abi.DarkStats()
+        _check(self.lib.rtx_group_device_dark_stats(self._g, r, C.byref(d)))
+        return _with_point_stats(s, p, d)
 
     def member(self, r):
         """what the runtime reports about member r (rtx_group_member_info): its device, its RCCL

@@ -250,6 +250,15 @@ typedef struct rtx_point_stats {
 	                                   * samples, so their packets run no shadow query at all */
 } rtx_point_stats;
 
+/* What RTX_OPT_SHADOW_DARK answered without a shadow query, only with count_traversal; a struct of
+ * its own for the same reason (rtx_get_dark_stats, after the render) */
+typedef struct rtx_dark_stats {
+	uint64_t shadow_dark_rays;        /* shadow rays of dark light samples (their terms are 0 whatever the ray
+	                                   * meets): not queried.  Packets the cone cull cleared are not looked at */
+	uint64_t shadow_dark_packet_rays; /* ... of which in packets of dark samples alone: no plane or object test
+	                                   * and no walk for the packet */
+} rtx_dark_stats;
+
 typedef struct rtx_ctx rtx_ctx;
 
 /* BVH builders for rtx_upload_scene (replacing accel_init, accel.c:266-315) */
@@ -276,6 +285,7 @@ int rtx_render_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *pa
 		      void *stream);
 int rtx_get_stats(const rtx_ctx *ctx, rtx_stats *out);
 int rtx_get_point_stats(const rtx_ctx *ctx, rtx_point_stats *out);
+int rtx_get_dark_stats(const rtx_ctx *ctx, rtx_dark_stats *out);
 /* Builder used by subsequent rtx_upload_scene calls on this context (RTX_BUILD_*). */
 int rtx_set_builder(rtx_ctx *ctx, int builder);
 
@@ -322,11 +332,18 @@ enum rtx_option {
 	                               * default: 1, up to 4 for batches of 16 packets per wave and more) */
 	RTX_OPT_RAYS_QUEUES = 13,     /* ray queries: atomic packet queues the waves are dealt over, 1..8 (0 =
 	                               * automatic, default: 8); any value gives the same hits */
-	RTX_OPT_SHADOW_POINT = 14     /* 1 (default): a shade point with 64 light samples or more decides once, per
+	RTX_OPT_SHADOW_POINT = 14,    /* 1 (default): a shade point with 64 light samples or more decides once, per
 	                               * emitter, that no sample's ray can meet a plane or an object k_shadow tests
 	                               * one by one; its packets then skip those tests, and a point clear of
 	                               * everything runs a loop with no shadow query (same image); 0: every packet
 	                               * tests them.  RTX_OPT_SHADOW_CULL 0 turns this off too */
+	RTX_OPT_SHADOW_DARK = 15      /* 1 (default): a light sample of a shade point with 64 samples or more whose
+	                               * diffuse and specular factors are both 0 (a light behind the surface, and
+	                               * no specular term toward the viewer) skips its shadow query: it adds +-0
+	                               * blocked or not (same image).  Only where shadow rays walk a tree and
+	                               * the cone cull has not cleared the packet, in scenes whose transmittances are
+	                               * finite with |kt| <= 1 and whose emitters are finite; 0: every sample is
+	                               * queried.  RTX_OPT_SHADOW_CULL 0 turns this off too */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -441,6 +458,9 @@ int rtx_group_device_stats(const rtx_group *g, int r, rtx_stats *out);
 /* rtx_point_stats of the last group render: summed over the devices, and device r's own */
 int rtx_group_get_point_stats(const rtx_group *g, rtx_point_stats *out);
 int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point_stats *out);
+/* rtx_dark_stats likewise */
+int rtx_group_get_dark_stats(const rtx_group *g, rtx_dark_stats *out);
+int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_stats *out);
 /* What the runtime reports about member r, read back rather than assumed (a line that claims N
  * devices can show that N communicators of one clique formed on N distinct devices) */
 typedef struct rtx_group_member {

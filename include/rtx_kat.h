@@ -38,6 +38,12 @@
  *                    (the listed record: rtype 0 the sphere (w0, rr), 1 the triangle w0 w1 w2, epsilon reps; clear:
  *                     the cone from P around the light misses the record's padded bounding sphere, formed as at
  *                     upload (rtx_quant.h rtx_record_sphere); blocks: the record's shadow test of that sample's ray)
+ * -- k_shadow's dark samples (rtx_shadow.hip dark_terms) against the terms they stand for --
+ * KAT_DARK   (19)    n3 view3 kd3 ks3 shin ldir3 ldist li3 att att_offset refl kt3 = 26  dark terms3 terms_kt3 = 7
+ *                    (att: RTX_ATT_*, refl: RTX_PHONG / RTX_BLINN, as floats; dark: dark_terms of the sample of
+ *                     direction ldir and length ldist, 0 when li is not finite or |kt| > 1 as the scene's flag
+ *                     has it; terms: shade_terms of the sample for li; terms_kt: for li * kt, the product a
+ *                     walk through one transparent surface leaves)
  * Texture records use the params' u32conv for the float->uint32 conversion.
  */
 #ifndef RTX_KAT_H
@@ -63,11 +69,12 @@ enum rtx_kat_kind {
 	RTX_KAT_BOX_Q8 = 16,
 	RTX_KAT_PLANE_CLEAR = 17,
 	RTX_KAT_LIN_CLEAR = 18,
-	RTX_KAT_NKINDS = 19,
+	RTX_KAT_DARK = 19,
+	RTX_KAT_NKINDS = 20,
 };
 #define RTX_KAT_FIRST_SHADOW RTX_KAT_ANY_TRI /* kinds >= this run in rtx_shadow.hip */
 
-static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28 };
-static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6 };
+static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26 };
+static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7 };
 
 #endif

@@ -6,7 +6,9 @@
  * point walking in lockstep, wave steps and leaf rounds.  Shade points are the primary hits of
  * sampled 1080p pixels and their -n 64 GI hits; light samples are i.i.d. like the library's
  * default RTX_RNG_COUNTER (W8SIM_STRAT=1: stratified like RTX_RNG_STRAT).  W8SIM_OCC=1 adds the
- * occluder-first tests (a cached opaque blocker tested before the walk).
+ * occluder-first tests (a cached opaque blocker tested before the walk).  Every run also evaluates
+ * k_shadow's dark predicate (RTX_OPT_SHADOW_DARK) per sample, Phong, and reports the dark rays and
+ * packets and what the packets' wave steps and leaf rounds come to without their dark lanes.
  *   build: tools/w8sim.sh       run: tools/w8sim <scene.json> [base_dir] [points]
  */
 #include <chrono>
@@ -71,9 +73,10 @@ static bool box_hit(const float lo[3], const float hi[3], const double o[3], con
 	return tn <= tf;
 }
 
-/* closest hit: t, the normal (unnormalised for triangles) */
-static bool closest(const Scene2 &S, const double o[3], const double d[3], double &tbest, double n[3])
+/* closest hit: t, the normal (unnormalised for triangles) and, when asked for, the object hit */
+static bool closest(const Scene2 &S, const double o[3], const double d[3], double &tbest, double n[3], uint32_t *obj_out = nullptr)
 {
+	uint32_t obj_hit = RTX_NONE;
 	tbest = 1e30;
 	bool hit = false;
 	for (uint32_t i = 0; i < S.sc->num_objects; i++) {
@@ -87,6 +90,7 @@ static bool closest(const Scene2 &S, const double o[3], const double d[3], doubl
 		if (t > 1e-4 && t < tbest) {
 			tbest = t;
 			hit = true;
+			obj_hit = i;
 			for (int k = 0; k < 3; k++)
 				n[k] = p.n[k];
 		}
@@ -110,6 +114,7 @@ static bool closest(const Scene2 &S, const double o[3], const double d[3], doubl
 				if (tri_hit(p, o, d, t) && t < tbest) {
 					tbest = t;
 					hit = true;
+					memcpy(&obj_hit, &p.b[3], 4);
 					n[0] = p.b[1] * p.c[2] - p.b[2] * p.c[1];
 					n[1] = p.b[2] * p.c[0] - p.b[0] * p.c[2];
 					n[2] = p.b[0] * p.c[1] - p.b[1] * p.c[0];
@@ -125,7 +130,28 @@ static bool closest(const Scene2 &S, const double o[3], const double d[3], doubl
 		if (box_hit(l1, h1, o, inv, tbest))
 			stk.push_back(nd.ref1);
 	}
+	if (obj_out)
+		*obj_out = obj_hit;
 	return hit;
+}
+
+/* k_shadow's dark predicate (rtx_shadow.hip dark_terms) for a shade point of normal n (facing the
+ * viewer), incoming direction view and material m, and a light sample of direction ldir, Phong:
+ * the diffuse factor is 0 (or the point has no diffuse colour) and so is the specular one */
+static bool sample_is_dark(const double n[3], const double view[3], const rtx_material &m, const double ldir[3])
+{
+	const double a = ldir[0] * n[0] + ldir[1] * n[1] + ldir[2] * n[2];
+	const bool kd0 = m.texture == RTX_TEX_UNIFORM && m.color[0][0] == 0 && m.color[0][1] == 0 && m.color[0][2] == 0;
+	const bool ks0 = m.ks[0] == 0 && m.ks[1] == 0 && m.ks[2] == 0;
+	if (!(a <= 0 || kd0))
+		return false;
+	double sm = 0;
+	for (int k = 0; k < 3; k++)
+		sm -= (2 * a * n[k] - ldir[k]) * view[k];
+	const double y = m.shininess;
+	const bool whole = rint(y) == y, odd = whole && rint(y / 2) != y / 2;
+	const bool pw0 = y != 0 && ((sm < 0 && (odd || !whole)) || (sm == 0 && y > 0));
+	return pw0 || (ks0 && !(sm == 0 && y < 0));
 }
 
 struct Stats {
@@ -458,6 +484,7 @@ int main(int argc, char **argv)
 	rtx_frame fr;
 	rtx_frame_setup(&sc->camera, 1920, 1080, &fr);
 	std::vector<std::array<float, 3>> pts;
+	std::vector<std::array<double, 7>> psh; /* per point: normal (facing the viewer), incoming direction, object */
 	const int gi = 64;
 	while ((int)pts.size() < npts) {
 		const uint32_t x = (uint32_t)(U(rng) * 1920) % 1920, y = (uint32_t)(U(rng) * 1080) % 1080;
@@ -470,7 +497,8 @@ int main(int argc, char **argv)
 		for (int a = 0; a < 3; a++)
 			d[a] /= sqrt(dn);
 		double t, n[3];
-		if (!closest(S2, o, d, t, n))
+		uint32_t ob1 = RTX_NONE;
+		if (!closest(S2, o, d, t, n, &ob1))
 			continue;
 		double P0[3], nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
 		for (int a = 0; a < 3; a++) {
@@ -481,6 +509,7 @@ int main(int argc, char **argv)
 			for (int a = 0; a < 3; a++)
 				n[a] = -n[a];
 		pts.push_back({ (float)P0[0], (float)P0[1], (float)P0[2] });
+		psh.push_back({ n[0], n[1], n[2], d[0], d[1], d[2], (double)ob1 });
 		for (int g = 0; g < gi && (int)pts.size() < npts; g++) {
 			double r[3], rn;
 			do {
@@ -497,8 +526,13 @@ int main(int argc, char **argv)
 				for (int a = 0; a < 3; a++)
 					r[a] = -r[a];
 			double t2, n2[3];
-			if (closest(S2, P0, r, t2, n2))
+			uint32_t ob2 = RTX_NONE;
+			if (closest(S2, P0, r, t2, n2, &ob2)) {
 				pts.push_back({ (float)(P0[0] + t2 * r[0]), (float)(P0[1] + t2 * r[1]), (float)(P0[2] + t2 * r[2]) });
+				const double l2 = sqrt(n2[0] * n2[0] + n2[1] * n2[1] + n2[2] * n2[2]);
+				const double sg = n2[0] * r[0] + n2[1] * r[1] + n2[2] * r[2] > 0 ? -1.0 / l2 : 1.0 / l2;
+				psh.push_back({ sg * n2[0], sg * n2[1], sg * n2[2], r[0], r[1], r[2], (double)ob2 });
+			}
 		}
 	}
 	/* the first opaque blocker of the segment P + t d (t < dist) in the walk's slot order (the
@@ -562,6 +596,9 @@ int main(int argc, char **argv)
 	const int order = getenv("W8SIM_ORDER") ? atoi(getenv("W8SIM_ORDER")) : 0;
 	const bool sort_samples = getenv("W8SIM_SORT") && atoi(getenv("W8SIM_SORT"));
 	const bool strat = getenv("W8SIM_STRAT") && atoi(getenv("W8SIM_STRAT")); /* RTX_RNG_STRAT light samples */
+	/* dark samples (RTX_OPT_SHADOW_DARK): rays, packets, and the wave steps / leaf rounds of the packets
+	 * with and without their dark lanes, over the points the cone does not clear (W8SIM_CONE=1) */
+	double dk_rays = 0, dk_all = 0, dk_pk = 0, dk_pk_all = 0, dk_steps[2] = { 0, 0 }, dk_rounds[2] = { 0, 0 };
 	uint32_t prev_lane_blk[64];
 	for (int l = 0; l < 64; l++)
 		prev_lane_blk[l] = RTX_NONE;
@@ -698,6 +735,7 @@ int main(int argc, char **argv)
 			double lane_invq[64][3], lane_oq[64][3], lane_tl[64];
 			float lane_d[64][3], lane_dist[64];
 			uint32_t maxv = 0, imm_len[64] = {};
+			bool lane_dark[64] = {};
 			for (uint32_t l = 0; l < 64 && b0 + l < nl; l++) {
 				const uint32_t j = b0 + l;
 				float u1 = su1[sord[j]], u2 = su2[sord[j]];
@@ -726,6 +764,8 @@ int main(int argc, char **argv)
 				for (int a = 0; a < 3; a++)
 					lane_d[l][a] = (float)d[a];
 				lane_dist[l] = (float)dist;
+				if ((uint32_t)psh[pi][6] != RTX_NONE)
+					lane_dark[l] = sample_is_dark(&psh[pi][0], &psh[pi][3], sc->materials[sc->objects[(uint32_t)psh[pi][6]].material], d);
 				blk_obj[l] = RTX_NONE;
 				double invq[3], oi[3], ob[3], db[3];
 				for (int a = 0; a < 3; a++) { /* the ray in the trees' frame (boxes); primitives in world space */
@@ -870,6 +910,30 @@ int main(int argc, char **argv)
 			for (uint32_t l = 0; l < 64 && b0 + l < nl; l++)
 				allseq.emplace_back(seq[l].begin(), seq[l].begin() + std::min<size_t>(seq[l].size(), imm_len[l]));
 			S.packets++;
+			if (!cone_sim || !cone_empty) {
+				const uint32_t nlanes = std::min<uint32_t>(64, nl - b0);
+				uint32_t nd = 0, mv[2] = { 0, 0 };
+				for (uint32_t l = 0; l < nlanes; l++) {
+					nd += lane_dark[l];
+					mv[0] = std::max(mv[0], imm_len[l]);
+					if (!lane_dark[l])
+						mv[1] = std::max(mv[1], imm_len[l]);
+				}
+				dk_rays += nd;
+				dk_all += nlanes;
+				dk_pk += nd == nlanes;
+				dk_pk_all++;
+				for (int v = 0; v < 2; v++) {
+					dk_steps[v] += mv[v];
+					for (uint32_t i = 0; i < mv[v]; i++) {
+						uint32_t m = 0;
+						for (uint32_t l = 0; l < nlanes; l++)
+							if (!(v && lane_dark[l]) && i < imm_len[l])
+								m = std::max(m, leaves[l][i]);
+						dk_rounds[v] += m;
+					}
+				}
+			}
 			if (occ_sim) {
 				const uint32_t nlanes = std::min<uint32_t>(64, nl - b0);
 				for (uint32_t l = 0; l < nlanes; l++)
@@ -1133,6 +1197,10 @@ int main(int argc, char **argv)
 			printf("  proved empty within %d levels: %.3f of points, %.3f of the wave steps\n", d, cp / npts, cw / S.wave_steps);
 		}
 	}
+	printf("dark samples (over the %s): %.4f of the rays, %.4f of the packets wholly dark; without the dark lanes the "
+	       "packets take %.4f of the wave steps and %.4f of the leaf rounds\n",
+	       cone_sim ? "points the cone does not clear" : "all points", dk_rays / std::max(1.0, dk_all), dk_pk / std::max(1.0, dk_pk_all),
+	       dk_steps[1] / std::max(1.0, dk_steps[0]), dk_rounds[1] / std::max(1.0, dk_rounds[0]));
 	printf("lane refill (a finished lane takes the point's next light sample when >= T lanes are idle), per point:\n"
 	       "   T   wave steps (uniform)   refill rounds   cost (178/divergent + 95/uniform step + 220/refill)\n");
 	for (int k = 0; k < 6; k++)
