@@ -72,6 +72,8 @@ extern "C" hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu
 extern "C" hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
 				      uint32_t queues, uint32_t grab, unsigned long long *ctr, uint32_t waves, int count, int any,
 				      hipStream_t stream);
+extern "C" hipError_t rtx_launch_shadow_rays(const DScene *S, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
+					     int slots, int count, uint32_t cus, hipStream_t stream);
 extern "C" hipError_t rtx_launch_frame_rays(const DFrame *F, float4 *rays, hipStream_t stream);
 extern "C" hipError_t rtx_raysort_temp_bytes(uint32_t n, size_t *bytes);
 extern "C" hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const float lo[3], const float hi[3],
@@ -1510,6 +1512,87 @@ extern "C" int rtx_get_ray_stats(const rtx_ctx *c, rtx_ray_stats *out)
 	if (!c || !out)
 		return fail(RTX_ERR_ARG, "null argument");
 	*out = c->ray_stats;
+	return RTX_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* shadow queries (include/rtx.h rtx_trace_shadow_rays)                     */
+/* ------------------------------------------------------------------------ */
+static_assert(sizeof(rtx_shadow_ray) == 32 && sizeof(rtx_shadow_result) == 16, "k_shadow_rays moves a ray as two float4, a result as one");
+
+extern "C" int rtx_trace_shadow_rays(rtx_ctx *c, uint64_t n, const rtx_shadow_ray *rays, rtx_shadow_result *results, uint32_t flags)
+{
+	if (!c)
+		return fail(RTX_ERR_ARG, "null context");
+	if (flags & ~(uint32_t)(RTX_SHADOW_RAYS_SLOTS | RTX_SHADOW_RAYS_COUNT))
+		return fail(RTX_ERR_ARG, "unknown shadow-query flags 0x%x", flags);
+	if (n > RTX_RAYS_MAX)
+		return fail(RTX_ERR_ARG, "%llu rays above the supported %u per call", (unsigned long long)n, RTX_RAYS_MAX);
+	if (n && (!rays || !results))
+		return fail(RTX_ERR_ARG, "null shadow ray / result buffer");
+	if (!c->have_scene)
+		return fail(RTX_ERR_STATE, "rtx_trace_shadow_rays before rtx_upload_scene");
+	rtx_shadow_ray_stats rs{};
+	if (!n) {
+		c->shadow_ray_stats = rs;
+		return RTX_OK;
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t stream = c->stream;
+	if (grow_bytes(c->d_qrays, c->qrays_bytes, (size_t)n * sizeof(rtx_shadow_ray)) != hipSuccess ||
+	    grow_bytes(c->d_qhits, c->qhits_bytes, (size_t)n * sizeof(rtx_shadow_result)) != hipSuccess)
+		return fail(RTX_ERR_NOMEM, "device copies of %llu shadow rays", (unsigned long long)n);
+	HIP_TRY(hipMemcpyAsync(c->d_qrays, rays, (size_t)n * sizeof(rtx_shadow_ray), hipMemcpyHostToDevice, stream));
+	/* the walk's LDS stack size and spill area as a render sets them (it does so at every render, in
+	 * the context's scene; a query may come first, so it sets its own copy) */
+	DScene S = c->scene;
+	S.w8lstk = c->opt_lstk;
+	S.w8spill = nullptr;
+	S.w8spill_lanes = 0;
+	if (S.w8 && S.w8depth > S.w8lstk + 1) {
+		uint32_t lanes = 0;
+		HIP_TRY(rtx_shadow_grid_lanes((uint32_t)c->cus, &lanes));
+		void *p = c->d_w8spill;
+		const hipError_t e = grow_bytes(p, c->w8spill_bytes, (size_t)lanes * (S.w8depth - 1 - S.w8lstk) * sizeof(uint32_t));
+		c->d_w8spill = (uint32_t *)p;
+		if (e != hipSuccess)
+			return fail(RTX_ERR_NOMEM, "lane-stack spill area: %s", hipGetErrorString(e));
+		S.w8spill = c->d_w8spill;
+		S.w8spill_lanes = lanes;
+	}
+	if (!c->d_rctr)
+		HIP_TRY(hipMalloc(&c->d_rctr, sizeof(unsigned long long) * RTX_RQ_N));
+	HIP_TRY(hipMemsetAsync(c->d_rctr, 0, sizeof(unsigned long long) * RTX_RQ_N, stream));
+	HIP_TRY(hipEventRecord(c->ev[0], stream));
+	HIP_TRY(rtx_launch_shadow_rays(&S, (const float4 *)c->d_qrays, (float4 *)c->d_qhits, (uint32_t)n, c->d_rctr,
+				       (flags & RTX_SHADOW_RAYS_SLOTS) != 0, (flags & RTX_SHADOW_RAYS_COUNT) != 0, (uint32_t)c->cus, stream));
+	HIP_TRY(hipEventRecord(c->ev[1], stream));
+	unsigned long long ctr[RTX_SQ_N];
+	HIP_TRY(hipMemcpyAsync(ctr, c->d_rctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipMemcpyAsync(results, c->d_qhits, (size_t)n * sizeof(rtx_shadow_result), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	float k = 0;
+	HIP_TRY(hipEventElapsedTime(&k, c->ev[0], c->ev[1]));
+	rs.rays = ctr[RTX_SQ_RAYS];
+	rs.blocked = ctr[RTX_SQ_BLOCKED];
+	rs.far_rays = ctr[RTX_SQ_FAR];
+	rs.box_tests = ctr[RTX_SQ_BOXES];
+	rs.tri_tests = ctr[RTX_SQ_TRIS];
+	rs.sphere_tests = ctr[RTX_SQ_SPHERES];
+	rs.wave_steps = ctr[RTX_SQ_STEPS];
+	rs.uniform_steps = ctr[RTX_SQ_UNIF];
+	rs.leaf_rounds = ctr[RTX_SQ_LEAFR];
+	rs.stack_spills = ctr[RTX_SQ_SPILL];
+	rs.kernel_ms = k;
+	c->shadow_ray_stats = rs;
+	return RTX_OK;
+}
+
+extern "C" int rtx_get_shadow_ray_stats(const rtx_ctx *c, rtx_shadow_ray_stats *out)
+{
+	if (!c || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = c->shadow_ray_stats;
 	return RTX_OK;
 }
 

@@ -364,4 +364,20 @@ enum {
 	RTX_RQ_N = RTX_RQ_HEADS + RTX_RQ_MAX_QUEUES * RTX_RQ_HEAD_STRIDE
 };
 
+/* counters of a shadow-ray query (k_shadow_rays, rtx_trace_shadow_rays), in the ray queries' buffer */
+enum {
+	RTX_SQ_RAYS = 0, /* live rays */
+	RTX_SQ_BLOCKED,
+	RTX_SQ_FAR,      /* RTX_SHADOW_RAYS_COUNT: as k_shadow's RTX_C_FARS, RTX_C_SBOXES, ... */
+	RTX_SQ_BOXES,
+	RTX_SQ_TRIS,
+	RTX_SQ_SPHERES,
+	RTX_SQ_STEPS,
+	RTX_SQ_UNIF,
+	RTX_SQ_LEAFR,
+	RTX_SQ_SPILL,
+	RTX_SQ_N
+};
+static_assert(RTX_SQ_N <= RTX_RQ_HEADS, "the shadow-ray counters live in the ray queries' buffer");
+
 #endif

@@ -128,6 +128,7 @@ struct rtx_ctx {
 	void *d_qrays = nullptr, *d_qhits = nullptr;
 	size_t qrays_bytes = 0, qhits_bytes = 0;
 	rtx_ray_stats ray_stats{};
+	rtx_shadow_ray_stats shadow_ray_stats{}; /* rtx_trace_shadow_rays */
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;

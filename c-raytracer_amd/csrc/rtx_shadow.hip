@@ -26,6 +26,10 @@
  * so the resident waves share one compact region of the tree in L2.  A point's
  * samples fill whole power-of-two lane slots and its sum runs inside one wave
  * in lane order, so its result does not depend on which wave takes it.
+ *
+ * k_shadow_rays: the same shadow query (shadow_query) on a caller's shadow rays
+ * (rtx_trace_shadow_rays), one 64-ray packet per wave, so tests can hold the walk
+ * to brute force ray by ray.
  */
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -1773,6 +1777,86 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 }
 
 /* ------------------------------------------------------------------------ */
+/* k_shadow_rays: shadow_query on a caller's rays (rtx_trace_shadow_rays)   */
+/* ------------------------------------------------------------------------ */
+/* One 64-ray packet per wave and turn, ray i in lane i % 64 of packet i / 64: k_shadow's workgroup
+ * (block size, LDS copies of the trees' top levels, lane stacks, argument block) around one call of
+ * shadow_query per packet, every plane and every listed record tested, nothing culled.  A workgroup
+ * takes packets blockIdx.x * RTX_SH_NW + wave, then strides by the grid, so the grid never exceeds
+ * the one the lane-stack spill area was sized for.  Rays are two float4 (origin, dist | direction,
+ * light object), results one (transmittance, blocked). */
+template <bool COUNT, int WALK, bool LA>
+__global__ __launch_bounds__(WAVE *RTX_SH_NW) void k_shadow_rays(KShadow ka, const float4 *__restrict__ rays, float4 *__restrict__ res,
+								 uint32_t n, unsigned long long *ctr)
+{
+	constexpr bool TOP = WALK == WALK_BVH2;
+	__shared__ uint4 top_q[TOP ? RTX_TOP_MAX : 1];
+	__shared__ uint32_t top_e[TOP ? RTX_TOP_MAX : 1];
+	__shared__ __attribute__((aligned(16))) uint32_t wstk[RTX_SH_NW][WALK == WALK_W8 ? RTX_W8_STACK + RTX_W8_TQ : 1][WAVE];
+	__shared__ KShadow ks_s;
+	__shared__ uint4 t8[WALK == WALK_W8 && RTX_W8_TOP ? RTX_W8_TOP_MAX * 4 : 1];
+	const uint32_t ntop = TOP ? ka.ntop : 0u;
+	for (uint32_t i = threadIdx.x; i < ntop; i += WAVE * RTX_SH_NW) {
+		top_q[i] = ldg4u(ka.top + 4 * i);
+		top_e[i] = gptr(ka.top)[4 * ntop + i];
+	}
+	const uint32_t nt8 = (WALK == WALK_W8 && RTX_W8_TOP) ? min(ka.w8top, (uint32_t)RTX_W8_TOP_MAX) : 0u;
+	for (uint32_t i = threadIdx.x; i < 4 * nt8; i += WAVE * RTX_SH_NW)
+		t8[i] = ldg4u((const uint32_t *)ka.w8 + 4 * i);
+	const uint32_t wv = uni(threadIdx.x / WAVE);
+	if (threadIdx.x == 0)
+		ks_s = ka;
+	__syncthreads();
+	KShadow &ks = ks_s;
+	lds_u32 *stk = (lds_u32 *)&wstk[wv][0][LA ? 0u : lane_id()];
+	ShadowCount sc = {};
+	u64 n_live = 0, n_blocked = 0;
+	const uint32_t packets = (n + WAVE - 1) / WAVE;
+	for (uint32_t pk = blockIdx.x * RTX_SH_NW + wv; pk < packets; pk += gridDim.x * RTX_SH_NW) {
+		reread_barrier();
+		const size_t i = (size_t)pk * WAVE + lane_id();
+		const bool in = i < n;
+		float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, __uint_as_float(RTX_NONE));
+		if (in) {
+			r0 = rays[2 * i];
+			r1 = rays[2 * i + 1];
+		}
+		/* an idle lane: dist <= 0 or NaN, or a NaN direction component */
+		const bool act = in && r0.w > 0.f && r1.x == r1.x && r1.y == r1.y && r1.z == r1.z;
+		const f3 o = act ? mk3(r0.x, r0.y, r0.z) : mk3(0.f, 0.f, 0.f);
+		const f3 d = act ? mk3(r1.x, r1.y, r1.z) : mk3(0.f, 0.f, 1.f);
+		const float dist = act ? r0.w : 0.f;
+		/* far as k_trace marks a shade point (sp_far) */
+		const f3 of = uni(ks.tf.rotated) ? tf_point(ks.tf.r, ks.tf.c, o) : o;
+		const bool far = act && tf_far(of, ks.tf.cf, ks.tf.rad);
+		f3 li = mk3(1.f, 1.f, 1.f);
+		const QBvh Q = make_qbvh<WALK>(ks, top_q, top_e, stk, t8, wv);
+		const bool blocked = shadow_query<COUNT, WALK, LA>(Q, unip(ks.recs), unip(ks.mats), unip(ks.planes), uni(ks.num_planes),
+								 unip(ks.lin), uni(ks.num_lin), uni(ks.have_tree) != 0, ks.tf, act, far, o, d,
+								 dist, __float_as_uint(r1.w), li, sc);
+		reread_barrier();
+		if (in)
+			res[i] = blocked ? make_float4(0.f, 0.f, 0.f, __uint_as_float(1u)) : make_float4(li.x, li.y, li.z, 0.f);
+		n_live += popc64(ballot(act));
+		n_blocked += popc64(ballot(blocked));
+	}
+	if (lane_id() == 0) {
+		atomicAdd(&ctr[RTX_SQ_RAYS], n_live);
+		atomicAdd(&ctr[RTX_SQ_BLOCKED], n_blocked);
+		if (COUNT) {
+			atomicAdd(&ctr[RTX_SQ_FAR], sc.far);
+			atomicAdd(&ctr[RTX_SQ_BOXES], sc.boxes);
+			atomicAdd(&ctr[RTX_SQ_TRIS], sc.tris);
+			atomicAdd(&ctr[RTX_SQ_SPHERES], sc.sph);
+			atomicAdd(&ctr[RTX_SQ_STEPS], sc.steps);
+			atomicAdd(&ctr[RTX_SQ_UNIF], sc.unif);
+			atomicAdd(&ctr[RTX_SQ_LEAFR], sc.lrounds);
+			atomicAdd(&ctr[RTX_SQ_SPILL], sc.spills);
+		}
+	}
+}
+
+/* ------------------------------------------------------------------------ */
 /* known answers of the fast device functions k_shadow runs (rtx_kat.h)     */
 /* ------------------------------------------------------------------------ */
 __global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in, float *__restrict__ out)
@@ -2058,15 +2142,12 @@ extern "C" hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes)
 	return e;
 }
 
-extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm,
-					uint32_t n_sp, uint32_t per_wave, uint32_t slot_b, float4 *contrib,
-					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream)
+/* the scene's part of k_shadow's arguments (trees, frames, records, the walk's LDS stack size): what
+ * rtx_launch_shadow and rtx_launch_shadow_rays share.  Checks what the kernels rely on: the top levels
+ * fit their LDS copy, the lane stack its LDS entries, and a deep 8-wide tree has a spill area for
+ * the largest grid */
+static hipError_t shadow_scene_args(const DScene *S, uint32_t cus, KShadow &ka)
 {
-	const uint32_t nw = per_wave ? (n_sp + per_wave - 1) / per_wave : 0u;
-	if (!slot_b || (slot_b & (slot_b - 1)) || slot_b > WAVE || !per_wave || per_wave > WAVE)
-		return hipErrorInvalidValue;
-	if (!nw)
-		return hipSuccess;
 	if (S->num_top > RTX_TOP_MAX)
 		return hipErrorInvalidValue;
 	const int walk = walk_of(S);
@@ -2081,14 +2162,13 @@ extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const
 		if (!S->w8spill || S->w8spill_lanes < lanes)
 			return hipErrorInvalidValue;
 	}
-	KShadow ka;
 	ka.prims = S->prims;
 	ka.recs = (const char *)S->nodes;
 	ka.qnodes = S->qnodes;
 	ka.top = S->top;
 	ka.ntop = S->num_top;
 	ka.tf = S->tf;
-for (int a = 0; a < 3; a++) {
+	for (int a = 0; a < 3; a++) {
 		ka.qo[a] = S->qo[a];
 		ka.qs[a] = S->qs[a];
 		ka.qsi[a] = 1.f / S->qs[a];
@@ -2096,21 +2176,9 @@ for (int a = 0; a < 3; a++) {
 	ka.mats = S->mats;
 	ka.planes = S->planes;
 	ka.emitters = S->emitters;
-	ka.sp = sp;
-	ka.perm = perm;
-	ka.contrib = contrib;
-	ka.ctr = ctr;
 	ka.have_tree = S->root_ref != RTX_EMPTY_REF && !S->lin && (S->w8 || S->qnodes); /* the walk of walk_of(S) has its tree */
 	ka.num_planes = S->num_planes;
 	ka.num_emitters = S->num_emitters;
-	ka.n_sp = n_sp;
-	ka.per_wave = per_wave;
-	ka.slot_b = slot_b;
-	ka.slot_lg = (uint32_t)__builtin_ctz(slot_b);
-	ka.rng = P->rng;
-	ka.attenuation = P->attenuation;
-	ka.reflection = P->reflection;
-	ka.att_offset = P->att_offset;
 	ka.w8 = S->w8;
 	ka.w8s = S->w8s;
 	ka.w8spill = S->w8spill;
@@ -2138,9 +2206,81 @@ for (int a = 0; a < 3; a++) {
 	/* the listed records' bounding spheres, when they are those of the records this walk lists */
 	ka.lsph = (const float4 *)S->lsph;
 	ka.num_lsph = (S->lsph && S->num_lsph == ka.num_lin) ? S->num_lsph : 0u;
-	if (walk == WALK_W8)
+	return hipSuccess;
+}
+
+extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm,
+					uint32_t n_sp, uint32_t per_wave, uint32_t slot_b, float4 *contrib,
+					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream)
+{
+	const uint32_t nw = per_wave ? (n_sp + per_wave - 1) / per_wave : 0u;
+	if (!slot_b || (slot_b & (slot_b - 1)) || slot_b > WAVE || !per_wave || per_wave > WAVE)
+		return hipErrorInvalidValue;
+	if (!nw)
+		return hipSuccess;
+	KShadow ka;
+	hipError_t e = shadow_scene_args(S, cus, ka);
+	if (e != hipSuccess)
+		return e;
+	ka.sp = sp;
+	ka.perm = perm;
+	ka.contrib = contrib;
+	ka.ctr = ctr;
+	ka.n_sp = n_sp;
+	ka.per_wave = per_wave;
+	ka.slot_b = slot_b;
+	ka.slot_lg = (uint32_t)__builtin_ctz(slot_b);
+	ka.rng = P->rng;
+	ka.attenuation = P->attenuation;
+	ka.reflection = P->reflection;
+	ka.att_offset = P->att_offset;
+	if (walk_of(S) == WALK_W8)
 		return launch_walk<WALK_W8>(ka, nw, cus, count, stream);
 	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream);
+}
+
+/* n caller's shadow rays through shadow_query (k_shadow_rays): the instance follows the scene as
+ * rtx_launch_shadow's does (walk_of; a tiny scene's list has no tree), `slots` picks the lane-slot
+ * kernels' stack addressing (LA), `count` the counting instance.  ctr: RTX_SQ_N zeroed counters. */
+template <bool C, int W, bool LA>
+static hipError_t launch_shadow_rays(const KShadow &ka, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
+				     uint32_t cus, uint32_t spill_lanes, hipStream_t stream)
+{
+	int per_cu = 0;
+	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_shadow_rays<C, W, LA>),
+								   WAVE * RTX_SH_NW, 0);
+	if (e != hipSuccess)
+		return e;
+	uint32_t grid = per_cu > 0 && cus > 0 ? (uint32_t)per_cu * cus : 1024u;
+	if (spill_lanes) /* no more workgroups than the spill area has lanes for (w8_spill_at) */
+		grid = grid < spill_lanes / (WAVE * RTX_SH_NW) ? grid : spill_lanes / (WAVE * RTX_SH_NW);
+	const uint32_t need = ((n + WAVE - 1) / WAVE + RTX_SH_NW - 1) / RTX_SH_NW;
+	grid = grid < need ? grid : need;
+	if (!grid)
+		return hipErrorInvalidValue;
+	hipLaunchKernelGGL((k_shadow_rays<C, W, LA>), dim3(grid), dim3(WAVE * RTX_SH_NW), 0, stream, ka, rays, res, n, ctr);
+	return hipGetLastError();
+}
+
+extern "C" hipError_t rtx_launch_shadow_rays(const DScene *S, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
+					     int slots, int count, uint32_t cus, hipStream_t stream)
+{
+	if (!n)
+		return hipSuccess;
+	KShadow ka{};
+	hipError_t e = shadow_scene_args(S, cus, ka);
+	if (e != hipSuccess)
+		return e;
+	const uint32_t spill = (walk_of(S) == WALK_W8 && S->w8depth > S->w8lstk + 1) ? S->w8spill_lanes : 0u;
+#define RTX_SR(C, W, LA) launch_shadow_rays<C, W, LA>(ka, rays, res, n, ctr, cus, spill, stream)
+	if (walk_of(S) == WALK_W8) {
+		if (count)
+			return slots ? RTX_SR(true, WALK_W8, true) : RTX_SR(true, WALK_W8, false);
+		return slots ? RTX_SR(false, WALK_W8, true) : RTX_SR(false, WALK_W8, false);
+	}
+	/* the BVH2 walk and the listed objects keep no lane stack: LA changes nothing there */
+	return count ? RTX_SR(true, WALK_BVH2, false) : RTX_SR(false, WALK_BVH2, false);
+#undef RTX_SR
 }
 
 /* the code object of this file on the current device, loaded now (rtx_open) rather than at the

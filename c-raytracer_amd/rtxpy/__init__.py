@@ -318,6 +318,31 @@ class Renderer:
         _check(self.lib.rtx_get_ray_stats(self._ctx, C.byref(s)))
         return s
 
+    def shadow_rays(self, origins, dirs, dist, light_object=-1, slots=False, count=False):
+        """rtx_trace_shadow_rays on host arrays: origins / dirs (n, 3), dist and light_object a scalar or (n,).
+        Ray i runs in lane i % 64 of packet i / 64.  Returns a dict of numpy arrays: blocked (n,) bool,
+        transmittance (n, 3) float32 ((0, 0, 0) where blocked)."""
+        origins = np.asarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+        if origins.shape != dirs.shape:
+            raise ValueError("origins and dirs differ in shape")
+        n = origins.shape[0]
+        rays = np.zeros(n, abi.SHADOW_RAY_DTYPE)
+        rays["origin"] = origins
+        rays["dir"] = dirs
+        rays["dist"] = np.asarray(dist, np.float32)
+        rays["light_object"] = np.asarray(light_object, np.int32)
+        res = np.zeros(n, abi.SHADOW_RESULT_DTYPE)
+        flags = (abi.RTX_SHADOW_RAYS_SLOTS if slots else 0) | (abi.RTX_SHADOW_RAYS_COUNT if count else 0)
+        _check(self.lib.rtx_trace_shadow_rays(self._ctx, n, rays.ctypes.data if n else None, res.ctypes.data if n else None,
+                                              flags))
+        return {"blocked": res["blocked"] != 0, "transmittance": res["transmittance"].copy()}
+
+    def shadow_ray_stats(self):
+        s = abi.ShadowRayStats()
+        _check(self.lib.rtx_get_shadow_ray_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)

@@ -143,6 +143,28 @@ class RayStats(C.Structure):
 RAY_DTYPE = [("origin", "<f4", 3), ("tmax", "<f4"), ("dir", "<f4", 3), ("pad_", "<u4")]
 HIT_DTYPE = [("t", "<f4"), ("object", "<i4"), ("material", "<i4"), ("outside", "<u4"), ("n", "<f4", 3), ("pad_", "<u4")]
 
+# shadow queries (rtx_trace_shadow_rays)
+RTX_SHADOW_RAYS_SLOTS, RTX_SHADOW_RAYS_COUNT = 1, 2
+
+
+class ShadowRay(C.Structure):
+    _fields_ = [("origin", F3), ("dist", C.c_float), ("dir", F3), ("light_object", C.c_int32)]
+
+
+class ShadowResult(C.Structure):
+    _fields_ = [("transmittance", F3), ("blocked", C.c_uint32)]
+
+
+class ShadowRayStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("blocked", C.c_uint64), ("far_rays", C.c_uint64), ("box_tests", C.c_uint64),
+                ("tri_tests", C.c_uint64), ("sphere_tests", C.c_uint64), ("wave_steps", C.c_uint64),
+                ("uniform_steps", C.c_uint64), ("leaf_rounds", C.c_uint64), ("stack_spills", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+
+SHADOW_RAY_DTYPE = [("origin", "<f4", 3), ("dist", "<f4"), ("dir", "<f4", 3), ("light_object", "<i4")]
+SHADOW_RESULT_DTYPE = [("transmittance", "<f4", 3), ("blocked", "<u4")]
+
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
     KAT_MORTON, KAT_U32, KAT_GI_DIR, KAT_REFRACT, KAT_ANY_TRI, KAT_SPH_LIGHT_SH, KAT_BOX_Q, KAT_SPEC_POW, \
@@ -161,7 +183,8 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_group_get_dark_stats", "rtx_group_device_dark_stats",
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
-               "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats"]
+               "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
+               "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -295,6 +318,10 @@ def declare_rtx(lib):
     lib.rtx_frame_rays_device.restype = C.c_int
     lib.rtx_get_ray_stats.argtypes = [C.c_void_p, C.POINTER(RayStats)]
     lib.rtx_get_ray_stats.restype = C.c_int
+    lib.rtx_trace_shadow_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.rtx_trace_shadow_rays.restype = C.c_int
+    lib.rtx_get_shadow_ray_stats.argtypes = [C.c_void_p, C.POINTER(ShadowRayStats)]
+    lib.rtx_get_shadow_ray_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

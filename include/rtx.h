@@ -417,6 +417,47 @@ typedef struct rtx_ray_stats {    /* the last rtx_trace_rays* of the context */
 int rtx_get_ray_stats(const rtx_ctx *ctx, rtx_ray_stats *out);
 
 /*
+ * Shadow queries: a caller's shadow rays through the render's own shadow query (k_shadow's
+ * shadow_query: the planes, the objects it tests one by one, the any-hit walk of the scene's shadow
+ * tree with its fast intersectors), with is_light_blocked's semantics (render.c:126-134).
+ * rtx_trace_rays(RTX_RAYS_ANY_HIT) answers with the closest-hit kernel's walk instead.
+ */
+typedef struct rtx_shadow_ray {   /* 32 B */
+	float origin[3];
+	float dist;               /* the segment's length (finite): objects count with eps < t < dist.  0, a negative
+	                           * value or NaN = an idle lane: unblocked, transmittance (1, 1, 1) */
+	float dir[3];             /* unit length; a NaN component = an idle lane */
+	int32_t light_object;     /* index of the object the ray is aimed at (never blocks or filters it), -1: none */
+} rtx_shadow_ray;
+typedef struct rtx_shadow_result { /* 16 B */
+	float transmittance[3];   /* not blocked: the product of kt over every transparent object hit, each once,
+	                           * from (1, 1, 1); blocked: (0, 0, 0) (the walk ends at the first opaque hit) */
+	uint32_t blocked;         /* 1: an opaque object other than light_object is hit with eps < t < dist */
+} rtx_shadow_result;
+enum {
+	RTX_SHADOW_RAYS_SLOTS = 1, /* the lane-slot kernels' lane-stack addressing (k_shadow for fewer than 64 lights) */
+	RTX_SHADOW_RAYS_COUNT = 2  /* fill the traversal counters of rtx_shadow_ray_stats (counting instance) */
+};
+/* n rays from / results to HOST buffers.  Ray i runs in lane i % 64 of the 64-ray packet i / 64, with
+ * no reordering: a caller chooses which rays share a wave (the walk specialises on a direction
+ * octant its live lanes share, takes scalar steps where they sit on one node, and runs its
+ * deferred rounds wave-wide), and a ray's result never depends on that choice.  A ray is far where
+ * its origin is (rtx_math.h tf_far, as the render marks a shade point).  Errors as rtx_trace_rays:
+ * n == 0 returns RTX_OK and launches nothing; RTX_ERR_STATE before an upload; RTX_ERR_ARG for a
+ * null buffer with n > 0, unknown flag bits or n > RTX_RAYS_MAX.  Touches neither rtx_stats nor
+ * the next render. */
+int rtx_trace_shadow_rays(rtx_ctx *ctx, uint64_t n, const rtx_shadow_ray *rays, rtx_shadow_result *results, uint32_t flags);
+typedef struct rtx_shadow_ray_stats { /* the last rtx_trace_shadow_rays of the context */
+	uint64_t rays, blocked;   /* live rays (not idle), blocked ones */
+	/* only with RTX_SHADOW_RAYS_COUNT (as rtx_stats' shadow counters) */
+	uint64_t far_rays;        /* far rays that reached the walk (run from the segment's other end) */
+	uint64_t box_tests, tri_tests, sphere_tests;
+	uint64_t wave_steps, uniform_steps, leaf_rounds, stack_spills;
+	double kernel_ms;         /* k_shadow_rays, HIP events */
+} rtx_shadow_ray_stats;
+int rtx_get_shadow_ray_stats(const rtx_ctx *ctx, rtx_shadow_ray_stats *out);
+
+/*
  * Several devices rendering one frame (the reference's own parallel point is
  * the OpenMP row loop of render.c:349-352).  The group builds the scene's BVHs once, on its
  * first device (rtx_upload_scene's work: device SAH build, 8-wide collapse), and the other

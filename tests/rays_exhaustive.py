@@ -36,23 +36,35 @@ SPONGE_MAT, DRAGON_MAT = 0, 2  # the materials tell the two meshes' triangles ap
 ROTATION = {"world": [0.0, 0.0, 0.0], "rotated": [-0.56, 0.56, 0.78]}  # "rotated": scene6.json's own
 
 
+def write_meshes(tmp):
+    """the two meshes under `tmp`/meshes; returns the scene template (scene6.json's camera and materials)"""
+    import standins
+    os.makedirs(os.path.join(str(tmp), "meshes"), exist_ok=True)
+    standins.write_stl(os.path.join(str(tmp), "meshes", "sponge2.stl"), standins.menger_standin(level=2))
+    standins.write_stl(os.path.join(str(tmp), "meshes", "dragon4.stl"), standins.dragon_standin(4))
+    with open(os.path.join(C.SCENES, "scene6.json")) as fh:
+        return json.load(fh)
+
+
+def mesh(f, m, r, s, p):
+    return {"type": "Mesh", "parameters": {"material": m, "filename": "meshes/" + f, "position": p, "rotation": r, "scale": s}}
+
+
+def mesh_objects(name):
+    """the sponge and the dragon of variant `name` (a key of ROTATION)"""
+    rot = ROTATION[name]
+    return [mesh("sponge2.stl", SPONGE_MAT, rot, 0.5, [0.0, -0.13, 2.4]),
+            mesh("dragon4.stl", DRAGON_MAT, rot if name == "rotated" else [1.57, 0.0, 0.0], 0.7, [2.0, 0.1, 2.9])]
+
+
 def write_scenes(tmp):
     """both scenes under `tmp` (a folder of the test session's): {name: path of its JSON}"""
-    import standins
     tmp = str(tmp)
-    os.makedirs(os.path.join(tmp, "meshes"), exist_ok=True)
-    standins.write_stl(os.path.join(tmp, "meshes", "sponge2.stl"), standins.menger_standin(level=2))
-    standins.write_stl(os.path.join(tmp, "meshes", "dragon4.stl"), standins.dragon_standin(4))
-    with open(os.path.join(C.SCENES, "scene6.json")) as fh:
-        tpl = json.load(fh)
+    tpl = write_meshes(tmp)
     out = {}
-    for name, rot in ROTATION.items():
+    for name in ROTATION:
         d = json.loads(json.dumps(tpl))
-        mesh = lambda f, m, r, s, p: {"type": "Mesh", "parameters": {"material": m, "filename": "meshes/" + f, "position": p,
-                                                                     "rotation": r, "scale": s}}
-        d["Objects"] = [
-            mesh("sponge2.stl", SPONGE_MAT, rot, 0.5, [0.0, -0.13, 2.4]),
-            mesh("dragon4.stl", DRAGON_MAT, rot if name == "rotated" else [1.57, 0.0, 0.0], 0.7, [2.0, 0.1, 2.9]),
+        d["Objects"] = mesh_objects(name) + [
             {"type": "Sphere", "parameters": {"material": 2, "position": [-1.6, 0.4, 2.2], "radius": 0.6}},
             {"type": "Sphere", "parameters": {"material": 1, "epsilon": 0.0003, "position": [0.4, 1.6, 1.5], "radius": 0.3,
                                               "lights": 4}},
@@ -374,6 +386,29 @@ def kat_pairs(kat, objs, o, d, pr, po):
         out = kat(kind, rec)
         hit[m], t[m] = out[:, 0] != 0, out[:, 1]
     return hit, t
+
+
+def any_pairs(kat, objs, o, d, dist, pr, po):
+    """the shadow query's own decisions on the pairs (ray pr[i], triangle or sphere po[i]) for segments
+    of length dist (per ray): the fused any-hit triangle test with tlim = dist (KAT_ANY_TRI), the sphere
+    test with t < dist (KAT_SPHERE).  Returns hit (m,) bool; pairs with a plane stay False."""
+    hit = np.zeros(len(pr), bool)
+    ty = objs["type"][po]
+    col = lambda x: x.reshape(len(x), -1)
+    dist = np.asarray(dist, np.float32)
+    m = np.nonzero(ty == abi.RTX_TRIANGLE)[0]
+    if len(m):
+        ob = objs[po[m]]
+        rec = np.concatenate([o[pr[m]], d[pr[m]]] + [col(ob[c]) for c in ("p0", "e1", "e2", "epsilon")] + [col(dist[pr[m]])],
+                             axis=1).astype(np.float32)
+        hit[m] = kat(abi.KAT_ANY_TRI, rec)[:, 0] != 0
+    m = np.nonzero(ty == abi.RTX_SPHERE)[0]
+    if len(m):
+        ob = objs[po[m]]
+        rec = np.concatenate([o[pr[m]], d[pr[m]]] + [col(ob[c]) for c in ("p0", "radius", "epsilon")], axis=1).astype(np.float32)
+        out = kat(abi.KAT_SPHERE, rec)
+        hit[m] = (out[:, 0] != 0) & (out[:, 1] < dist[pr[m]])
+    return hit
 
 
 def all_pairs(n_rays, n_objs):
