@@ -33,7 +33,8 @@ extern "C" hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const D
 				       hipStream_t stream);
 extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm,
 					uint32_t n_sp, uint32_t per_wave, uint32_t slot_b, float4 *contrib,
-					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream);
+					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream, uint32_t *pmask,
+					int *premasked);
 extern "C" hipError_t rtx_launch_post(uint32_t w, uint32_t h, const rtx_post *pp, float *rgb, const float *z,
 				      int *rad, float4 *pv, unsigned *scratch, hipStream_t stream);
 extern "C" hipError_t rtx_spsort_temp_bytes(uint32_t n, size_t *bytes);
@@ -192,6 +193,7 @@ extern "C" void rtx_close(rtx_ctx *c)
 	dfree(c->d_staging);
 	dfree(c->d_sp);
 	dfree(c->d_contrib);
+	dfree(c->d_pmask);
 	dfree(c->d_tile_rec);
 	for (auto &e : c->ev)
 		if (e)
@@ -1151,7 +1153,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 
 	HIP_TRY(hipEventRecord(c->ev0, stream));
 	double t_trace = 0, t_sort = 0, t_shadow = 0, t_accum = 0;
-	uint64_t shade_points = 0;
+	uint64_t shade_points = 0, premask_points = 0;
 	uint32_t chunks = 0;
 	unsigned long long tot[RTX_C_N] = {}; /* counters of the chunks that completed */
 	/* shadow kernel: lane slots of slot_b = pow2ceil(lights) (<= 64) lanes per point; ~16 packets per wave */
@@ -1182,6 +1184,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		HIP_TRY(grow(c->d_staging, c->staging_bytes, (size_t)waves * staging_cap * 6 * sizeof(float4)));
 		HIP_TRY(grow(c->d_sp, c->sp_bytes, (size_t)sp_cap * 6 * sizeof(float4)));
 		HIP_TRY(grow(c->d_contrib, c->contrib_bytes, (size_t)sp_cap * sizeof(float4)));
+		if (c->opt_premask) /* 4 B per point beside the 128 budgeted above, out of the two thirds of HBM left free */
+			HIP_TRY(grow(c->d_pmask, c->pmask_bytes, (size_t)sp_cap * sizeof(uint32_t)));
 		HIP_TRY(grow(c->d_tile_rec, c->tile_rec_bytes, (size_t)(end - begin) * sizeof(uint2)));
 		HIP_TRY(hipMemsetAsync(c->d_ctr, 0, sizeof(unsigned long long) * RTX_C_N, stream));
 		HIP_TRY(hipEventRecord(c->ev[0], stream));
@@ -1234,8 +1238,12 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		Ssh.cull_slots = c->opt_cull == 2 ? 1u : 0u;
 		Ssh.point = (c->opt_cull && c->opt_point) ? 1u : 0u; /* RTX_OPT_SHADOW_POINT */
 		Ssh.dark = (c->opt_cull && c->opt_dark) ? 1u : 0u;   /* RTX_OPT_SHADOW_DARK */
+		int premasked = 0; /* RTX_OPT_SHADOW_PREMASK: k_point_masks ran for this chunk */
 		HIP_TRY(rtx_launch_shadow(&Ssh, &P, c->d_sp, perm, n_sp, per_wave, slot_b, c->d_contrib, c->d_ctr,
-					  p->count_traversal, (uint32_t)c->cus, stream));
+					  p->count_traversal, (uint32_t)c->cus, stream, c->opt_premask ? c->d_pmask : nullptr,
+					  &premasked));
+		if (premasked)
+			premask_points += n_sp;
 		HIP_TRY(hipEventRecord(c->ev[2], stream));
 		HIP_TRY(rtx_launch_accum(&F, &P, c->d_tile_rec, c->d_contrib, begin, end - begin, d_rgb, stream));
 		HIP_TRY(hipEventRecord(c->ev[3], stream));
@@ -1290,6 +1298,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	c->pstats.shadow_point_clear = ctr[RTX_C_SPCLEAR];
 	c->dstats.shadow_dark_rays = ctr[RTX_C_SDARK];
 	c->dstats.shadow_dark_packet_rays = ctr[RTX_C_SDARKPK];
+	c->mstats.premask_points = premask_points;
 	st.node_visits = ctr[RTX_C_NODES] + st.shadow_node_visits;
 	st.tri_tests = ctr[RTX_C_TRIS] + ctr[RTX_C_STRIS];
 	st.sphere_tests = ctr[RTX_C_SPHERES] + ctr[RTX_C_SSPHERES];
@@ -1747,6 +1756,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow dark samples %lld is not 0 or 1", (long long)value);
 		c->opt_dark = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_PREMASK:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow pre-mask %lld is not 0 or 1", (long long)value);
+		c->opt_premask = (int)value;
+		return RTX_OK;
 	}
 	return fail(RTX_ERR_ARG, "unknown option %d", option);
 }
@@ -1791,6 +1805,14 @@ extern "C" int rtx_get_dark_stats(const rtx_ctx *c, rtx_dark_stats *out)
 	if (!c || !out)
 		return fail(RTX_ERR_ARG, "null argument");
 	*out = c->dstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_get_premask_stats(const rtx_ctx *c, rtx_premask_stats *out)
+{
+	if (!c || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = c->mstats;
 	return RTX_OK;
 }
 

@@ -67,6 +67,7 @@ struct rtx_group {
 	rtx_stats stats{};
 	rtx_point_stats pstats{};
 	rtx_dark_stats dstats{};
+	rtx_premask_stats mstats{};
 };
 
 extern "C" void rtx_group_close(rtx_group *g)
@@ -500,6 +501,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	rtx_stats s = c0->stats;
 	rtx_point_stats ps = c0->pstats;
 	rtx_dark_stats ds = c0->dstats;
+	rtx_premask_stats ms = c0->mstats;
 	for (int r = 1; r < n; r++) {
 		const rtx_stats &o = g->ctx[r]->stats;
 		s.closest_rays += o.closest_rays;
@@ -528,6 +530,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 		ps.shadow_point_clear += g->ctx[r]->pstats.shadow_point_clear;
 		ds.shadow_dark_rays += g->ctx[r]->dstats.shadow_dark_rays;
 		ds.shadow_dark_packet_rays += g->ctx[r]->dstats.shadow_dark_packet_rays;
+		ms.premask_points += g->ctx[r]->mstats.premask_points;
 		s.waves += o.waves;
 		s.chunks += o.chunks;
 		s.kernel_ms = std::max(s.kernel_ms, o.kernel_ms);
@@ -543,6 +546,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	g->stats = s;
 	g->pstats = ps;
 	g->dstats = ds;
+	g->mstats = ms;
 	return RTX_OK;
 }
 
@@ -587,6 +591,24 @@ extern "C" int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_s
 	if (r < 0 || r >= g->n)
 		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
 	*out = g->ctx[r]->dstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_get_premask_stats(const rtx_group *g, rtx_premask_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = g->mstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_device_premask_stats(const rtx_group *g, int r, rtx_premask_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (r < 0 || r >= g->n)
+		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
+	*out = g->ctx[r]->mstats;
 	return RTX_OK;
 }
 

@@ -100,6 +100,8 @@ struct rtx_ctx {
 	size_t sp_bytes = 0;
 	float4 *d_contrib = nullptr;
 	size_t contrib_bytes = 0;
+	uint32_t *d_pmask = nullptr; /* the chunk's per-point masks, a word per record (k_point_masks) */
+	size_t pmask_bytes = 0;
 	uint2 *d_tile_rec = nullptr;
 	size_t tile_rec_bytes = 0;
 	/* shade points per tile seen by the last render of this scene with the same GI / bounce
@@ -123,6 +125,7 @@ struct rtx_ctx {
 	rtx_stats stats{};
 	rtx_point_stats pstats{}; /* rtx_get_point_stats */
 	rtx_dark_stats dstats{};  /* rtx_get_dark_stats */
+	rtx_premask_stats mstats{}; /* rtx_get_premask_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
 	unsigned long long *d_rctr = nullptr;
 	void *d_qrays = nullptr, *d_qhits = nullptr;
@@ -145,7 +148,8 @@ struct rtx_ctx {
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
 	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	int opt_dark = 1;         /* RTX_OPT_SHADOW_DARK: light samples that add nothing skip their shadow query */
-	uint32_t mem_share = 1;   /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
+	int opt_premask = 1;      /* RTX_OPT_SHADOW_PREMASK: the per-point masks formed before k_shadow, one point per lane */
+	uint32_t mem_share = 1;  /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */
 };
 

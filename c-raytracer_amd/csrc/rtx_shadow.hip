@@ -792,6 +792,7 @@ const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi
 	uint32_t w8lstk;      /* lane-stack entries in LDS */
 	uint32_t w8top;       /* entries of the 8-wide tree's top levels, copied to LDS per workgroup (DScene.w8top) */
 	uint32_t w8sph;       /* the 8-wide tree holds spheres (DScene.w8sph) */
+	uint32_t dark;        /* RTX_OPT_SHADOW_DARK (and the scene allows it, DScene.dark_ok): dark samples skip their query */
 	const DEmitter *lin;  /* objects shadow_query tests one by one: the emitters the 8-wide tree leaves out,
 	                       * or every bounded object of a tiny scene (no tree walk) */
 	uint32_t num_lin;
@@ -816,7 +817,8 @@ const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi
 	const float4 *lsph;   /* DScene.lsph: the bounding spheres of the `lin` records (point_masks) */
 	uint32_t num_lsph;    /* num_lin when they are there, else 0 */
 	uint32_t point;       /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
-	uint32_t dark;        /* RTX_OPT_SHADOW_DARK (and the scene allows it, DScene.dark_ok): dark samples skip their query */
+	const uint32_t *pm;   /* the points' masks formed before the kernel (k_point_masks), by record index; null:
+	                       * k_shadow forms them itself (point_masks) */
 };
 
 __device__ __forceinline__ void reread_barrier() { asm volatile("" ::: "memory"); }
@@ -1212,6 +1214,91 @@ __device__ __forceinline__ PointMasks point_masks(const KShadow &ks, f3 p, uint3
 	return m;
 }
 
+/* point_masks ahead of k_shadow (RTX_OPT_SHADOW_PREMASK), one shade point per lane: in point_masks a
+ * whole wave works on one point, and all but its two sphere passes is wave-uniform arithmetic done 64
+ * times over for one answer.  Here lane i takes record i of the chunk and walks the emitters, the
+ * planes, the cull spheres and the listed records' spheres in turn, each read through the scalar
+ * cache at a wave-uniform index, through the very functions point_masks calls (this file's compile
+ * flags, -ffp-contract=off, hold for both), so every predicate has the same operands and the same
+ * answer.  Scenes of at most 8 emitters only: the word written for record i is
+ * cone | pln << 8 | lin << 16 | smp << 24, bit e of each byte for emitter e, and 0 for a far point
+ * (point_masks gives a far point no mask).  k_shadow reads it where it would call point_masks.
+ * Every shade point has a light sample (k_trace emits no other), so a point that is not far samples
+ * some emitter and its smp byte is not 0: the byte tells the far points apart. */
+#define RTX_PM_BLOCK 256
+__global__ __launch_bounds__(RTX_PM_BLOCK) void k_point_masks(KShadow ks, uint32_t *__restrict__ out)
+{
+	const uint32_t i = blockIdx.x * RTX_PM_BLOCK + threadIdx.x;
+	const bool own = i < ks.n_sp;
+	const float4 *rec = ks.sp + (size_t)(own ? i : ks.n_sp - 1u) * SPREC;
+	const float4 q0 = ldg4(rec, 0), q4 = ldg4(rec, 64);
+	const f3 p = mk3(q0.x, q0.y, q0.z);
+	const uint32_t ow = __float_as_uint(q4.x), obj = ow & ~RTX_SP_FAR;
+	const bool live = own && !(ow & RTX_SP_FAR);
+	const bool pt = ks.point != 0;
+	const uint32_t n = min(ks.num_cull, (uint32_t)WAVE);
+	const uint32_t ne = min(ks.num_emitters, 8u);
+	const uint32_t num_lin = ks.num_lin, num_planes = ks.num_planes;
+	const uint32_t nr = pt ? min(ks.num_lsph, (uint32_t)WAVE) : 0u;
+	const bool lin_ok = pt && nr == num_lin;
+	uint32_t cone = 0u, pln = 0u, lin = 0u, smp = 0u;
+	for (uint32_t e = 0; e < ne; e++) {
+		const DEmitter E = emitter_uni(ks.emitters + e);
+		const uint32_t bit = 1u << e;
+		if (E.obj != obj)
+			smp |= bit;
+		f3 lc;
+		float lr;
+		emitter_sphere(E, lc, lr);
+		const f3 ax0 = sub3(lc, p);
+		const float L = sqrtf(magsqr3(ax0));
+		if (pt) {
+			bool pc = true;
+			for (uint32_t k = 0; k < num_planes; k++) {
+				const auto *pl = cptr(ks.planes) + k;
+				pc = plane_clear(mk3(pl->n[0], pl->n[1], pl->n[2]), pl->d, pl->eps, p, lc, lr, L) && pc;
+			}
+			if (pc)
+				pln |= bit;
+			if (!num_lin)
+				lin |= bit;
+		}
+		/* a lane whose point has no cone toward e (at or inside the light's sphere) counts as met */
+		const bool go = live && L > 1.01f * lr;
+		if ((!n && !nr) || !ballot(go))
+			continue;
+		const Cone c = cone_of(p, lc, lr, ax0, L);
+		if (n) {
+			/* four spheres a turn, their scalar loads issued together (one wait, not four; past the
+			 * last sphere the last one again), until every lane of the wave has met one */
+			bool meets = !go;
+			for (uint32_t k = 0; k < n && ballot(!meets); k += 4) {
+				f4v s[4];
+#pragma unroll
+				for (uint32_t j = 0; j < 4; j++)
+					s[j] = *(const __attribute__((address_space(4))) f4v *)(ks.cull + min(k + j, n - 1u));
+#pragma unroll
+				for (uint32_t j = 0; j < 4; j++)
+					meets = cone_meets<false>(c, p, make_float4(s[j].x, s[j].y, s[j].z, s[j].w)) || meets;
+			}
+			if (!meets)
+				cone |= bit;
+		}
+		if (lin_ok && nr) {
+			bool meets = !go;
+			for (uint32_t k = 0; k < nr && ballot(!meets); k++) {
+				const uint32_t ro = cptr((const uint32_t *)(ks.lin + k))[0]; /* DEmitter.obj */
+				const f4v s = *(const __attribute__((address_space(4))) f4v *)(ks.lsph + k);
+				meets = meets || (ro != E.obj && cone_meets<true>(c, p, make_float4(s.x, s.y, s.z, s.w)));
+			}
+			if (!meets)
+				lin |= bit;
+		}
+	}
+	if (own)
+		out[i] = live ? (cone | pln << 8 | lin << 16 | smp << 24) : 0u;
+}
+
 /* The lane-slot path's cone mask (RTX_SH_SLOTCULL): each lane tests its own point's cones (emitters
  * e < 8) against every sphere in turn, the sphere and the emitter read through the scalar cache;
  * bit e set when no sphere meets.  A packet whose every live lane is clear for its emitter skips
@@ -1556,7 +1643,25 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 				reread_barrier();
 				const uint32_t nl = uni(nls[k]);
 				const float4 *rec = unip(ks.sp) + (size_t)uni(sid[k]) * SPREC;
-				{
+				if (const uint32_t *pm = unip(ks.pm)) {
+					/* the masks k_point_masks formed for this record, one scalar load: a byte each for
+					 * cone, planes, listed objects and sampled emitters (at most 8 emitters), handed over
+					 * as point_masks' are below.  The smp byte is 0 for a far point only */
+					const uint32_t w = cptr(pm)[uni(sid[k])];
+					const bool tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK;
+					const uint32_t smp = w >> 24, ok = (w >> 8) & (w >> 16) & (tree ? w : ~0u) & 0xffu;
+					const bool ac = uni(ks.point) != 0 && smp && !(smp & ~ok);
+					if (lane_id() == 0) {
+						wt_w[wv].cm[0] = w & 0xffu;
+						wt_w[wv].cm[1] = 0u;
+						wt_w[wv].cm[2] = (w >> 8) & 0xffu;
+						wt_w[wv].cm[3] = 0u;
+						wt_w[wv].cm[4] = (w >> 16) & 0xffu;
+						wt_w[wv].cm[5] = 0u;
+						wt_w[wv].cm[6] = ac ? 1u : 0u;
+					}
+					lds_sync();
+				} else {
 					/* the point through vector loads made uniform, not the scalar loads light_sample
 					 * makes: shared with them, the point was live from here and the compiler hoisted
 					 * the far path's double-precision copies of it out of the packet loop and
@@ -2211,8 +2316,11 @@ static hipError_t shadow_scene_args(const DScene *S, uint32_t cus, KShadow &ka)
 
 extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm,
 					uint32_t n_sp, uint32_t per_wave, uint32_t slot_b, float4 *contrib,
-					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream)
+					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream, uint32_t *pmask,
+					int *premasked)
 {
+	if (premasked)
+		*premasked = 0;
 	const uint32_t nw = per_wave ? (n_sp + per_wave - 1) / per_wave : 0u;
 	if (!slot_b || (slot_b & (slot_b - 1)) || slot_b > WAVE || !per_wave || per_wave > WAVE)
 		return hipErrorInvalidValue;
@@ -2234,6 +2342,19 @@ extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const
 	ka.attenuation = P->attenuation;
 	ka.reflection = P->reflection;
 	ka.att_offset = P->att_offset;
+	/* the points' masks ahead of the kernel (k_point_masks, pmask: a word per record of the chunk): where
+	 * k_shadow would form them, one point per wave (the wave-uniform packets), and a byte per mask holds
+	 * the emitters; else k_shadow forms them itself */
+	ka.pm = nullptr;
+	if (pmask && slot_b == WAVE && ka.num_emitters <= 8u && (ka.num_cull || ka.point)) {
+		hipLaunchKernelGGL(k_point_masks, dim3((n_sp + RTX_PM_BLOCK - 1) / RTX_PM_BLOCK), dim3(RTX_PM_BLOCK), 0, stream, ka, pmask);
+		e = hipGetLastError();
+		if (e != hipSuccess)
+			return e;
+		ka.pm = pmask;
+		if (premasked)
+			*premasked = 1;
+	}
 	if (walk_of(S) == WALK_W8)
 		return launch_walk<WALK_W8>(ka, nw, cus, count, stream);
 	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream);

@@ -203,13 +203,16 @@ def write_stl(path, tris):
     _check_scene(scene_lib().rtx_stl_write(os.fsencode(path), tris.shape[0], tris.ctypes.data))
 
 
-def _with_point_stats(s, p, d=None):
-    """the rtx_point_stats (and rtx_dark_stats) counters as attributes of the Stats beside them"""
+def _with_point_stats(s, p, d=None, m=None):
+    """the rtx_point_stats (and rtx_dark_stats, rtx_premask_stats) counters as attributes of the Stats beside them"""
     for f, _ in abi.PointStats._fields_:
         setattr(s, f, getattr(p, f))
     if d is not None:
         for f, _ in abi.DarkStats._fields_:
             setattr(s, f, getattr(d, f))
+    if m is not None:
+        for f, _ in abi.PremaskStats._fields_:
+            setattr(s, f, getattr(m, f))
     return s
 
 
@@ -280,7 +283,9 @@ class Renderer:
         _check(self.lib.rtx_get_point_stats(self._ctx, C.byref(p)))
         d = abi.DarkStats()
         _check(self.lib.rtx_get_dark_stats(self._ctx, C.byref(d)))
-        return _with_point_stats(s, p, d)
+        m = abi.PremaskStats()
+        _check(self.lib.rtx_get_premask_stats(self._ctx, C.byref(m)))
+        return _with_point_stats(s, p, d, m)
 
     def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
         """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
@@ -426,7 +431,9 @@ class Group:
         _check(self.lib.rtx_group_get_point_stats(self._g, C.byref(p)))
         d = abi.DarkStats()
         _check(self.lib.rtx_group_get_dark_stats(self._g, C.byref(d)))
-        return _with_point_stats(s, p, d)
+        m = abi.PremaskStats()
+        _check(self.lib.rtx_group_get_premask_stats(self._g, C.byref(m)))
+        return _with_point_stats(s, p, d, m)
 
     def device_stats(self, r):
         s = Stats()
@@ -435,7 +442,9 @@ class Group:
         _check(self.lib.rtx_group_device_point_stats(self._g, r, C.byref(p)))
         d = abi.DarkStats()
         _check(self.lib.rtx_group_device_dark_stats(self._g, r, C.byref(d)))
-        return _with_point_stats(s, p, d)
+        m = abi.PremaskStats()
+        _check(self.lib.rtx_group_device_premask_stats(self._g, r, C.byref(m)))
+        return _with_point_stats(s, p, d, m)
 
     def member(self, r):
         """what the runtime reports about member r (rtx_group_member_info): its device, its RCCL

@@ -89,6 +89,11 @@ class DarkStats(C.Structure):
     _fields_ = [("shadow_dark_rays", C.c_uint64), ("shadow_dark_packet_rays", C.c_uint64)]
 
 
+class PremaskStats(C.Structure):
+    """rtx_premask_stats: whether RTX_OPT_SHADOW_PREMASK took effect (rtxpy's stats() set it on the Stats they return)"""
+    _fields_ = [("premask_points", C.c_uint64)]
+
+
 RTX_TRANSPORT_NONE, RTX_TRANSPORT_RCCL, RTX_TRANSPORT_LOOPBACK, RTX_TRANSPORT_RCCL_SELF = 0, 1, 2, 3
 
 
@@ -106,7 +111,7 @@ RTX_FRAME_AUTO, RTX_FRAME_WORLD = 0, 1
 RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_OPT_SHADOW_GRAB, \
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
     RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES, \
-    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
+    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 
@@ -176,11 +181,12 @@ KAT_NAMES = ["moller", "sphere", "plane", "slab", "noise", "texture", "sph_light
 
 # symbols include/rtx.h declares (checked by tests/test_abi.py)
 RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload_scene", "rtx_render",
-               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
+               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_premask_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
                "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree",
                "rtx_group_set_builder", "rtx_group_set_option", "rtx_group_upload_scene", "rtx_group_render", "rtx_group_get_stats", "rtx_group_device_stats",
                "rtx_group_get_point_stats", "rtx_group_device_point_stats",
                "rtx_group_get_dark_stats", "rtx_group_device_dark_stats",
+               "rtx_group_get_premask_stats", "rtx_group_device_premask_stats",
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
                "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
@@ -244,6 +250,8 @@ def declare_rtx(lib):
     lib.rtx_get_point_stats.restype = C.c_int
     lib.rtx_get_dark_stats.argtypes = [C.c_void_p, C.POINTER(DarkStats)]
     lib.rtx_get_dark_stats.restype = C.c_int
+    lib.rtx_get_premask_stats.argtypes = [C.c_void_p, C.POINTER(PremaskStats)]
+    lib.rtx_get_premask_stats.restype = C.c_int
     lib.rtx_close.argtypes = [C.c_void_p]
     lib.rtx_close.restype = None
     lib.rtx_last_error.argtypes = []
@@ -289,6 +297,10 @@ def declare_rtx(lib):
     lib.rtx_group_get_dark_stats.restype = C.c_int
     lib.rtx_group_device_dark_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(DarkStats)]
     lib.rtx_group_device_dark_stats.restype = C.c_int
+    lib.rtx_group_get_premask_stats.argtypes = [C.c_void_p, C.POINTER(PremaskStats)]
+    lib.rtx_group_get_premask_stats.restype = C.c_int
+    lib.rtx_group_device_premask_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(PremaskStats)]
+    lib.rtx_group_device_premask_stats.restype = C.c_int
     lib.rtx_group_member_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(GroupMember)]
     lib.rtx_group_member_info.restype = C.c_int
     lib.rtx_group_close.argtypes = [C.c_void_p]

@@ -259,6 +259,13 @@ typedef struct rtx_dark_stats {
 	                                   * and no walk for the packet */
 } rtx_dark_stats;
 
+/* Whether RTX_OPT_SHADOW_PREMASK took effect, with or without count_traversal; a struct of its own for
+ * the same reason (rtx_get_premask_stats, after the render) */
+typedef struct rtx_premask_stats {
+	uint64_t premask_points; /* shade points whose masks were formed ahead of k_shadow (every point of the
+	                          * frame, or 0: the option is off or the scene is not one it applies to) */
+} rtx_premask_stats;
+
 typedef struct rtx_ctx rtx_ctx;
 
 /* BVH builders for rtx_upload_scene (replacing accel_init, accel.c:266-315) */
@@ -286,6 +293,7 @@ int rtx_render_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *pa
 int rtx_get_stats(const rtx_ctx *ctx, rtx_stats *out);
 int rtx_get_point_stats(const rtx_ctx *ctx, rtx_point_stats *out);
 int rtx_get_dark_stats(const rtx_ctx *ctx, rtx_dark_stats *out);
+int rtx_get_premask_stats(const rtx_ctx *ctx, rtx_premask_stats *out);
 /* Builder used by subsequent rtx_upload_scene calls on this context (RTX_BUILD_*). */
 int rtx_set_builder(rtx_ctx *ctx, int builder);
 
@@ -337,13 +345,18 @@ enum rtx_option {
 	                               * one by one; its packets then skip those tests, and a point clear of
 	                               * everything runs a loop with no shadow query (same image); 0: every packet
 	                               * tests them.  RTX_OPT_SHADOW_CULL 0 turns this off too */
-	RTX_OPT_SHADOW_DARK = 15      /* 1 (default): a light sample of a shade point with 64 samples or more whose
+	RTX_OPT_SHADOW_DARK = 15,     /* 1 (default): a light sample of a shade point with 64 samples or more whose
 	                               * diffuse and specular factors are both 0 (a light behind the surface, and
 	                               * no specular term toward the viewer) skips its shadow query: it adds +-0
 	                               * blocked or not (same image).  Only where shadow rays walk a tree and
 	                               * the cone cull has not cleared the packet, in scenes whose transmittances are
 	                               * finite with |kt| <= 1 and whose emitters are finite; 0: every sample is
 	                               * queried.  RTX_OPT_SHADOW_CULL 0 turns this off too */
+	RTX_OPT_SHADOW_PREMASK = 16   /* 1 (default): the masks of RTX_OPT_SHADOW_CULL and RTX_OPT_SHADOW_POINT are formed
+	                               * by a kernel of their own ahead of k_shadow, one shade point per lane, where
+	                               * k_shadow would form them one point per wave (points with 64 light samples
+	                               * or more) and the scene has at most 8 emitters (same masks, same image);
+	                               * 0: k_shadow forms them itself */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -502,6 +515,9 @@ int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point_stats *out
 /* rtx_dark_stats likewise */
 int rtx_group_get_dark_stats(const rtx_group *g, rtx_dark_stats *out);
 int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_stats *out);
+/* rtx_premask_stats likewise */
+int rtx_group_get_premask_stats(const rtx_group *g, rtx_premask_stats *out);
+int rtx_group_device_premask_stats(const rtx_group *g, int r, rtx_premask_stats *out);
 /* What the runtime reports about member r, read back rather than assumed (a line that claims N
  * devices can show that N communicators of one clique formed on N distinct devices) */
 typedef struct rtx_group_member {
