@@ -132,6 +132,15 @@ struct rtx_ctx {
 	size_t qrays_bytes = 0, qhits_bytes = 0;
 	rtx_ray_stats ray_stats{};
 	rtx_shadow_ray_stats shadow_ray_stats{}; /* rtx_trace_shadow_rays */
+	/* denoiser (rtx_frame_features*, rtx_denoise*): grow-only scratch of its own */
+	void *d_dn_rays = nullptr, *d_dn_hits = nullptr; /* the frame's rays and their closest hits */
+	size_t dn_rays_bytes = 0, dn_hits_bytes = 0;
+	void *d_dn_work = nullptr;                       /* the filter's 16-byte records (rtx_launch_denoise) */
+	size_t dn_work_bytes = 0;
+	void *d_dn_feat = nullptr, *d_dn_rgb = nullptr;  /* the host-buffer calls' device copies */
+	size_t dn_feat_bytes = 0, dn_rgb_bytes = 0;
+	unsigned long long *d_dn_ctr = nullptr;          /* k_dn_pack's hit-pixel count */
+	rtx_denoise_stats dn_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;

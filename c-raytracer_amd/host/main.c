@@ -17,6 +17,7 @@
  *   --rng strat    the same stream with the light samples stratified (opt-in, another estimator)
  *   --u32 wrap   float->uint32 texture conversion of a generic x86-64 build
  *                (default: AVX-512 saturating, like -march=native on AVX-512 hosts)
+ *   --denoise    the rendered rgb through rtx_frame_features + rtx_denoise (defaults) before it is saved
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -46,7 +47,8 @@ static const char *HELPTEXT =
 	"[-p] (\"real\" | \"cpu\")            : DEFAULT = real    : time to print with status messages.\n"
 	"[-g] (string)                    : DEFAULT = ambient : global illumination model (ambient | path).\n"
 	"[-f]                             : DEFAULT = OFF     : save raw output for post-processing.\n"
-	"[--gpus N] [--device D] [--seed S] [--rng counter|strat|const] [--u32 sat|wrap]\n";
+	"[--gpus N] [--device D] [--seed S] [--rng counter|strat|const] [--u32 sat|wrap]\n"
+	"[--denoise]                      : DEFAULT = OFF     : filter the image with the edge-aware denoiser before saving.\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -150,6 +152,31 @@ int main(int argc, char **argv)
 		LOG("Gathered %d shards in %.3f ms.", ngpu, st.gather_ms);
 	LOG("Rays: %llu closest + %llu shadow in %.3f ms device time (%.1f Mrays/s).", (unsigned long long)closest,
 	    (unsigned long long)shadow, kms, kms > 0 ? (closest + shadow) / (kms * 1e3) : 0.0);
+
+	if (argv_find(argc, argv, "--denoise", 0)) {
+		/* a context of its own on the first device: the frame's feature records, then the filter with its
+		 * defaults over the gathered rgb (z is left as rendered) */
+		LOG("Denoising.");
+		rtx_ctx *ctx = NULL;
+		rtx_feature *feat = malloc(px * sizeof(rtx_feature));
+		rtx_denoise_params dp;
+		rtx_denoise_stats ds;
+		rtx_denoise_params_default(&dp);
+		if (!feat) {
+			LOG("Unable to allocate the feature buffer.");
+			return 1;
+		}
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_frame_features(ctx, &fr, p.u32conv, feat) ||
+		    rtx_denoise(ctx, w, h, &dp, feat, rgb) || rtx_get_denoise_stats(ctx, &ds)) {
+			LOG("%s", rtx_last_error());
+			rtx_close(ctx);
+			return 1;
+		}
+		rtx_close(ctx);
+		free(feat);
+		LOG("Denoised %llu hit pixels: features %.3f ms, %u filter levels %.3f ms.", (unsigned long long)ds.hit_pixels,
+		    ds.features_ms, ds.iterations, ds.filter_ms);
+	}
 
 	LOG("Saving image.");
 	const char *out = argv[2];

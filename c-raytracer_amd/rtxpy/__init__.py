@@ -348,6 +348,53 @@ class Renderer:
         _check(self.lib.rtx_get_shadow_ray_stats(self._ctx, C.byref(s)))
         return s
 
+    def features(self, frame, u32conv=abi.RTX_U32_SAT):
+        """rtx_frame_features: the frame's primary-hit feature records, a structured (h, w) array of
+        abi.FEATURE_DTYPE (position, z, normal, material, albedo, object)."""
+        out = np.zeros((frame.height, frame.width), abi.FEATURE_DTYPE)
+        _check(self.lib.rtx_frame_features(self._ctx, C.byref(frame), u32conv, out.ctypes.data))
+        return out
+
+    def features_device(self, frame, d_features, u32conv=abi.RTX_U32_SAT, stream=None):
+        """rtx_frame_features_device: d_features is a device pointer (int) to width * height rtx_feature
+        records (12 float32 words each); stream: hipStream_t as int or None."""
+        _check(self.lib.rtx_frame_features_device(self._ctx, C.byref(frame), u32conv, C.c_void_p(d_features),
+                                                  C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def denoise_params(**params):
+        """rtx_denoise_params_default plus overrides (iterations, sigma_color / _normal / _albedo / _plane)"""
+        p = abi.DenoiseParams()
+        rtx_lib().rtx_denoise_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    def denoise(self, rgb, features, **params):
+        """rtx_denoise on host arrays: rgb (h, w, 3) float32, features the (h, w) array of features();
+        returns the filtered copy."""
+        out = np.ascontiguousarray(rgb, dtype=np.float32).copy()
+        feat = np.ascontiguousarray(features, dtype=abi.FEATURE_DTYPE)
+        h, w = out.shape[:2]
+        if feat.shape != (h, w):
+            raise ValueError("features and rgb differ in shape")
+        p = self.denoise_params(**params)
+        _check(self.lib.rtx_denoise(self._ctx, w, h, C.byref(p), feat.ctypes.data, out.ctypes.data))
+        return out
+
+    def denoise_device(self, width, height, d_features, d_rgb, stream=None, **params):
+        """rtx_denoise_device: d_features / d_rgb are device pointers (ints); d_rgb is filtered in place."""
+        p = self.denoise_params(**params)
+        _check(self.lib.rtx_denoise_device(self._ctx, width, height, C.byref(p), C.c_void_p(d_features), C.c_void_p(d_rgb),
+                                           C.c_void_p(stream) if stream else None))
+
+    def denoise_stats(self):
+        s = abi.DenoiseStats()
+        _check(self.lib.rtx_get_denoise_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)

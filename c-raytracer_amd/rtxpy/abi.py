@@ -170,6 +170,28 @@ class ShadowRayStats(C.Structure):
 SHADOW_RAY_DTYPE = [("origin", "<f4", 3), ("dist", "<f4"), ("dir", "<f4", 3), ("light_object", "<i4")]
 SHADOW_RESULT_DTYPE = [("transmittance", "<f4", 3), ("blocked", "<u4")]
 
+# denoiser (rtx_frame_features*, rtx_denoise*)
+class Feature(C.Structure):
+    _fields_ = [("position", F3), ("z", C.c_float), ("normal", F3), ("material", C.c_int32), ("albedo", F3),
+                ("object", C.c_int32)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_plane", C.c_float)]
+
+
+class DenoiseStats(C.Structure):
+    _fields_ = [("features_ms", C.c_double), ("filter_ms", C.c_double), ("pixels", C.c_uint64),
+                ("hit_pixels", C.c_uint64), ("iterations", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+# numpy view of rtx_feature arrays (the same 48-byte layout)
+FEATURE_DTYPE = [("position", "<f4", 3), ("z", "<f4"), ("normal", "<f4", 3), ("material", "<i4"), ("albedo", "<f4", 3),
+                 ("object", "<i4")]
+# rtx_denoise_params_default
+DENOISE_DEFAULTS = {"iterations": 1, "sigma_color": 0.004, "sigma_normal": 0.05, "sigma_albedo": 0.1, "sigma_plane": 0.02}
+
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
     KAT_MORTON, KAT_U32, KAT_GI_DIR, KAT_REFRACT, KAT_ANY_TRI, KAT_SPH_LIGHT_SH, KAT_BOX_Q, KAT_SPEC_POW, \
@@ -190,7 +212,9 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
                "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
-               "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats"]
+               "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats",
+               "rtx_frame_features_device", "rtx_frame_features", "rtx_denoise_params_default", "rtx_denoise_device",
+               "rtx_denoise", "rtx_get_denoise_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -334,6 +358,19 @@ def declare_rtx(lib):
     lib.rtx_trace_shadow_rays.restype = C.c_int
     lib.rtx_get_shadow_ray_stats.argtypes = [C.c_void_p, C.POINTER(ShadowRayStats)]
     lib.rtx_get_shadow_ray_stats.restype = C.c_int
+    lib.rtx_frame_features_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rtx_frame_features_device.restype = C.c_int
+    lib.rtx_frame_features.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p]
+    lib.rtx_frame_features.restype = C.c_int
+    lib.rtx_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+    lib.rtx_denoise_params_default.restype = None
+    lib.rtx_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+    lib.rtx_denoise_device.restype = C.c_int
+    lib.rtx_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
+    lib.rtx_denoise.restype = C.c_int
+    lib.rtx_get_denoise_stats.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
+    lib.rtx_get_denoise_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

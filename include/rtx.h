@@ -577,6 +577,64 @@ int rtx_postprocess_device(rtx_ctx *ctx, uint32_t width, uint32_t height, const 
 			   const void *d_z, void *stream);
 
 /*
+ * Denoiser: per-pixel feature records of a frame's primary hits, and an edge-aware
+ * a-trous filter of an rgb frame guided by them.  The features are a closest query of the frame's
+ * own rays (rtx_frame_rays_device, then the ray queries' kernel), so z is the render's z buffer bit
+ * for bit; a feature call renders nothing and leaves rtx_get_stats, rtx_get_ray_stats and the next
+ * render as they were.  The filter needs no uploaded scene (like rtx_postprocess).
+ */
+typedef struct rtx_feature {      /* 48 B, one per pixel, row-major, row 0 = top */
+	float position[3];        /* P = dir * t + origin, formed as the renderer's shade point; 0 on a miss */
+	float z;                  /* the primary hit's t (the render's z buffer); 0 on a miss */
+	float normal[3];          /* rtx_hit.n; 0 on a miss */
+	int32_t material;         /* -1 on a miss */
+	float albedo[3];          /* the material's texture colour at P (material.c:152-200), the colour the renderer
+	                           * shades the point with; 0 on a miss */
+	int32_t object;           /* -1 on a miss */
+} rtx_feature;
+/* The frame's width * height records into a DEVICE buffer (16-byte aligned), enqueued on `stream` (NULL =
+ * the context's own); synchronises it.  u32conv: enum rtx_u32conv, as rtx_params.u32conv of the render.
+ * Errors as rtx_frame_rays_device, RTX_ERR_STATE before an upload, RTX_ERR_ARG for another u32conv. */
+int rtx_frame_features_device(rtx_ctx *ctx, const rtx_frame *frame, int32_t u32conv, void *d_features, void *stream);
+/* Same into a HOST buffer. */
+int rtx_frame_features(rtx_ctx *ctx, const rtx_frame *frame, int32_t u32conv, rtx_feature *features);
+
+/*
+ * The filter: for level k = 0 .. iterations-1, step s = 2^k and sigma_c,k = sigma_color * 2^-k.  With c
+ * the level's input colour and f the features, a pixel i with f_i.z == 0 or a non-finite component of
+ * c_i keeps c_i's bits.  Otherwise, over the taps (u, v) in {-2..2}^2 with j = i + (u s, v s) inside
+ * the frame, f_j.z != 0 and c_j finite:
+ *     e = |c_i-c_j|^2 / sigma_c,k^2 + |n_i-n_j|^2 / sigma_normal^2 + |a_i-a_j|^2 / sigma_albedo^2
+ *       + (n_i . (P_j-P_i))^2 / (sigma_plane z_i)^2
+ *     w = h[u] h[v] exp(-e),  h = (1/16, 1/4, 3/8, 1/4, 1/16),   out_i = sum w c_j / sum w
+ * (n the normal, a the albedo, P the position).  Deterministic: two runs give the same bits.
+ */
+typedef struct rtx_denoise_params {
+	uint32_t iterations;      /* 1..8, default 1 */
+	float sigma_color, sigma_normal, sigma_albedo, sigma_plane;   /* each > 0; INFINITY switches its term off.  Defaults
+	                           * 0.004 / 0.05 / 0.1 / 0.02; sigma_color is in the frame's own radiance units (the
+	                           * default suits raw frames of the order of 1e-4: scale it with the frame) */
+} rtx_denoise_params;
+void rtx_denoise_params_default(rtx_denoise_params *p);
+/* d_features: w * h rtx_feature records, d_rgb: 3 floats per pixel, in/out; DEVICE buffers (d_features 16-byte
+ * aligned), enqueued on `stream` (NULL = the context's own); synchronises it.  RTX_ERR_ARG for iterations
+ * outside 1..8, a sigma <= 0 or NaN, a null buffer, w * h == 0 or above RTX_RAYS_MAX. */
+int rtx_denoise_device(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_denoise_params *params, const void *d_features,
+		       void *d_rgb, void *stream);
+/* Same on HOST buffers. */
+int rtx_denoise(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_denoise_params *params, const rtx_feature *features,
+		float *rgb);
+typedef struct rtx_denoise_stats {
+	double features_ms;       /* device time of the last rtx_frame_features*: rays, closest query, records (HIP events) */
+	double filter_ms;         /* device time of the last rtx_denoise*: every level (HIP events) */
+	uint64_t pixels;          /* of the last call of either kind */
+	uint64_t hit_pixels;      /* ... of which z != 0 */
+	uint32_t iterations;      /* levels the last rtx_denoise* ran */
+	uint32_t pad_;
+} rtx_denoise_stats;
+int rtx_get_denoise_stats(const rtx_ctx *ctx, rtx_denoise_stats *out);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
