@@ -29,6 +29,7 @@
 
 #include "rtx.h"
 #include "rtx_device.h"
+#include "rtx_launch.h"
 
 #define LB_LEAF 0x80000000u /* child encoding during the build: LB_LEAF | sorted primitive index */
 

@@ -28,6 +28,7 @@
 
 #include "rtx.h"
 #include "rtx_device.h"
+#include "rtx_launch.h"
 #include "rtx_math.h"
 
 static_assert(sizeof(rtx_feature) == 48, "k_dn_features writes a feature record as three float4");

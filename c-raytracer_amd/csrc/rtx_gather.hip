@@ -6,6 +6,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include "rtx_launch.h"
 #include "rtx_tiles.h"
 
 __global__ void k_tile_pack(const float *__restrict__ rgb, const float *__restrict__ z, uint32_t w, uint32_t h,

@@ -41,11 +41,6 @@
 #include "rtx_internal.h"
 #include "rtx_tiles.h"
 
-extern "C" hipError_t rtx_launch_tile_pack(const float *rgb, const float *z, uint32_t w, uint32_t h, uint32_t off,
-					   uint32_t stride, float4 *out, hipStream_t stream);
-extern "C" hipError_t rtx_launch_tile_unpack(const float4 *in, uint32_t w, uint32_t h, uint32_t off, uint32_t stride,
-					     float *rgb, float *z, hipStream_t stream);
-
 #define NCCL_TRY(expr)                                                                                  \
 	do {                                                                                            \
 		ncclResult_t r_ = (expr);                                                               \
@@ -376,18 +371,6 @@ static int grow_recs(float4 *&p, size_t &have, size_t need)
 	return RTX_OK;
 }
 
-static int ensure_fb(rtx_ctx *c, size_t px)
-{
-	if (px <= c->fb_pixels)
-		return RTX_OK;
-	dfree(c->d_rgb);
-	dfree(c->d_z);
-	HIP_TRY(hipMalloc(&c->d_rgb, px * 3 * sizeof(float)));
-	HIP_TRY(hipMalloc(&c->d_z, px * sizeof(float)));
-	c->fb_pixels = px;
-	return RTX_OK;
-}
-
 extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_params *p, float *rgb, float *z)
 {
 	if (!g || !fr || !p)
@@ -402,9 +385,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	const size_t px = (size_t)w * h;
 	for (rtx_ctx *c : g->ctx) {
 		HIP_TRY(hipSetDevice(c->device));
-		int rc = ensure_fb(c, px);
-		if (rc)
-			return rc;
+		HIP_TRY(rtx_ensure_framebuffer(c, px));
 	}
 	/* every shard on its own host thread (rtx_render_common synchronises its stream) */
 	std::vector<int> rcs(n, RTX_OK);

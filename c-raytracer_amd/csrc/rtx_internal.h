@@ -1,6 +1,9 @@
 /*
- * Library-internal declarations shared by rtx_api.cpp (single-device C-ABI) and rtx_group.cpp
- * (multi-device C-ABI): the device context, a host-built scene, and the render entry.
+ * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
+ * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
+ * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser)
+ * and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
+ * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
 #ifndef RTX_INTERNAL_H
@@ -11,10 +14,12 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "rtx.h"
 #include "rtx_device.h"
+#include "rtx_launch.h"
 
 /* sets the calling thread's rtx_last_error() message, returns code */
 int rtx_fail(int code, const char *fmt, ...);
@@ -33,6 +38,35 @@ template <class T> static inline void dfree(T *&p)
 		(void)hipFree(p);
 	p = nullptr;
 }
+
+/* Device scratch and its owner: the pointer and its capacity in bytes.  It only grows, converts
+ * to its pointer where a launcher or a copy takes one, and is freed with whatever holds it: a
+ * context (rtx_ctx's grow-only work buffers), or a scope (a build's temporaries, freed on every
+ * exit).  The device it was allocated on must be current when it is freed. */
+template <class T> struct RTX_HIDDEN DevBuf {
+	T *p = nullptr;
+	size_t bytes = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	~DevBuf() { dfree(p); }
+	/* room for `need` bytes; the contents do not survive a growth, and a failed one leaves the
+	 * buffer empty with capacity 0, so no later, smaller request takes a null pointer for room */
+	hipError_t grow(size_t need)
+	{
+		if (need <= bytes)
+			return hipSuccess;
+		dfree(p);
+		bytes = 0;
+		const hipError_t e = hipMalloc(&p, need);
+		if (e == hipSuccess)
+			bytes = need;
+		else
+			p = nullptr;
+		return e;
+	}
+	operator T *() const { return p; }
+};
 
 /* a host vector into a fresh device buffer, copied on `stream` (the context's own: no
  * synchronisation with the null stream) and complete on return */
@@ -60,6 +94,34 @@ template <class T> static inline int upload(T *&dst, const std::vector<T> &v, hi
 	return RTX_OK;
 }
 
+/* a scoped temporary: the vector into d, which frees the buffer with its scope */
+template <class T> static inline int upload(DevBuf<T> &d, const std::vector<T> &v, hipStream_t stream)
+{
+	d.bytes = 0;
+	const int rc = upload(d.p, v, stream);
+	if (!rc)
+		d.bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
+	return rc;
+}
+
+/* measurement builds (EXTRA=-DRTX_MEASURE=1): host-side phase times of an upload on stderr */
+#if RTX_MEASURE
+struct PhaseClock {
+	std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+	void mark(const char *what, hipStream_t st)
+	{
+		(void)hipStreamSynchronize(st);
+		const auto n = std::chrono::steady_clock::now();
+		fprintf(stderr, "[rtx upload] %-24s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
+		t = n;
+	}
+};
+#define PHASE(clk, what, st) clk.mark(what, st)
+#else
+struct PhaseClock {};
+#define PHASE(clk, what, st) ((void)clk)
+#endif
+
 /* the settings a render's shade points per tile depend on (rtx_ctx.sp_tile_key) */
 struct SpKey {
 	uint32_t v[21] = {};
@@ -67,13 +129,32 @@ struct SpKey {
 	bool operator==(const SpKey &o) const { return set && o.set && std::equal(v, v + 21, o.v); }
 };
 
-struct rtx_ctx {
-	int device = 0;
-	int builder = RTX_BUILD_SAH_GPU; /* the host's SAH tree, built on the device (29 vs 343 ms on the dragon) */
+/* a context's stream and events.  A base of rtx_ctx, so that they are destroyed after its members:
+ * rtx_close frees the buffers first, then the events and the stream. */
+struct RTX_HIDDEN CtxHandles {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+	CtxHandles() = default;
+	CtxHandles(const CtxHandles &) = delete;
+	CtxHandles &operator=(const CtxHandles &) = delete;
+	~CtxHandles()
+	{
+		for (hipEvent_t e : { ev[0], ev[1], ev[2], ev[3], ev[4], ev0, ev1 })
+			if (e)
+				(void)hipEventDestroy(e);
+		if (stream)
+			(void)hipStreamDestroy(stream);
+	}
+};
+
+struct rtx_ctx : CtxHandles {
+	RTX_HIDDEN ~rtx_ctx() = default; /* out of the library's exported symbols, like every new internal one */
+	int device = 0;
+	int builder = RTX_BUILD_SAH_GPU; /* the host's SAH tree, built on the device (29 vs 343 ms on the dragon) */
 	int cus = 0;
-	/* scene */
+	/* scene: exact-size buffers that change hands between the builder, a group and the context
+	 * (rtx_upload.cpp rtx_free_scene) */
 	DNode *d_nodes = nullptr;
 	DPlane *d_planes = nullptr;
 	DMaterial *d_mats = nullptr;
@@ -83,63 +164,47 @@ struct rtx_ctx {
 	uint32_t *d_top = nullptr;
 	DW8 *d_w8 = nullptr;
 	DW8S *d_w8s = nullptr;
-	uint32_t *d_w8spill = nullptr; /* k_shadow lane-stack spill of deep 8-wide trees (DScene.w8spill) */
 	float4 *d_cull = nullptr;      /* the 8-wide tree's top-level bounding spheres (DScene.cull) */
 	float4 *d_lsph = nullptr;      /* the listed records' bounding spheres (DScene.lsph) */
-	size_t w8spill_bytes = 0;
 	DScene scene{};
 	bool have_scene = false;
 	/* work buffers (grow-only) */
-	DTask *d_tasks = nullptr;
-	size_t task_bytes = 0;
-	uint32_t *d_ostk = nullptr; /* k_trace lane-stack overflow (DScene.ostk) */
-	size_t ostk_bytes = 0;
-	float4 *d_staging = nullptr;
-	size_t staging_bytes = 0;
-	float4 *d_sp = nullptr;
-	size_t sp_bytes = 0;
-	float4 *d_contrib = nullptr;
-	size_t contrib_bytes = 0;
-	uint32_t *d_pmask = nullptr; /* the chunk's per-point masks, a word per record (k_point_masks) */
-	size_t pmask_bytes = 0;
-	uint2 *d_tile_rec = nullptr;
-	size_t tile_rec_bytes = 0;
+	DevBuf<DTask> d_tasks;
+	DevBuf<uint32_t> d_ostk;    /* k_trace lane-stack overflow (DScene.ostk) */
+	DevBuf<uint32_t> d_w8spill; /* k_shadow lane-stack spill of deep 8-wide trees (DScene.w8spill) */
+	DevBuf<float4> d_staging;
+	DevBuf<float4> d_sp;
+	DevBuf<float4> d_contrib;
+	DevBuf<uint32_t> d_pmask; /* the chunk's per-point masks, a word per record (k_point_masks) */
+	DevBuf<uint2> d_tile_rec;
 	/* shade points per tile seen by the last render of this scene with the same GI / bounce
 	 * settings: sizes the next render's chunks (the static estimate is 5x too high on scene6) */
 	double sp_tile_seen = 0.0;
 	SpKey sp_tile_key{};
-	uint32_t *d_sortbuf = nullptr; /* keys0 | keys1 | vals0 | vals1 (shade-point sort) */
-	size_t sortbuf_bytes = 0;
-	void *d_sorttmp = nullptr;
-	size_t sorttmp_bytes = 0;
-	int *d_post_rad = nullptr; /* postprocess: per-pixel DoF radius, pv, scratch */
-	float4 *d_post_pv = nullptr;
-	size_t post_pixels = 0;
-	unsigned *d_post_scratch = nullptr;
+	DevBuf<uint32_t> d_sortbuf; /* keys0 | keys1 | vals0 | vals1 (shade-point sort) */
+	DevBuf<void> d_sorttmp;
+	DevBuf<int> d_post_rad; /* postprocess: per-pixel DoF radius, pv, scratch */
+	DevBuf<float4> d_post_pv;
+	DevBuf<unsigned> d_post_scratch;
 	float bound_lo[3] = { 0, 0, 0 }, bound_hi[3] = { 0, 0, 0 }; /* bounded objects' box */
-	hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
 	uint32_t total_lights = 0;
-	unsigned long long *d_ctr = nullptr;
-	float *d_rgb = nullptr, *d_z = nullptr;
-	size_t fb_pixels = 0;
+	DevBuf<unsigned long long> d_ctr;
+	DevBuf<float> d_rgb, d_z; /* the host-buffer calls' framebuffer (rtx_ensure_framebuffer) */
 	rtx_stats stats{};
 	rtx_point_stats pstats{}; /* rtx_get_point_stats */
 	rtx_dark_stats dstats{};  /* rtx_get_dark_stats */
 	rtx_premask_stats mstats{}; /* rtx_get_premask_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
-	unsigned long long *d_rctr = nullptr;
-	void *d_qrays = nullptr, *d_qhits = nullptr;
-	size_t qrays_bytes = 0, qhits_bytes = 0;
+	DevBuf<unsigned long long> d_rctr;
+	DevBuf<float4> d_qrays, d_qhits;
 	rtx_ray_stats ray_stats{};
 	rtx_shadow_ray_stats shadow_ray_stats{}; /* rtx_trace_shadow_rays */
 	/* denoiser (rtx_frame_features*, rtx_denoise*): grow-only scratch of its own */
-	void *d_dn_rays = nullptr, *d_dn_hits = nullptr; /* the frame's rays and their closest hits */
-	size_t dn_rays_bytes = 0, dn_hits_bytes = 0;
-	void *d_dn_work = nullptr;                       /* the filter's 16-byte records (rtx_launch_denoise) */
-	size_t dn_work_bytes = 0;
-	void *d_dn_feat = nullptr, *d_dn_rgb = nullptr;  /* the host-buffer calls' device copies */
-	size_t dn_feat_bytes = 0, dn_rgb_bytes = 0;
-	unsigned long long *d_dn_ctr = nullptr;          /* k_dn_pack's hit-pixel count */
+	DevBuf<float4> d_dn_rays, d_dn_hits; /* the frame's rays and their closest hits */
+	DevBuf<float4> d_dn_work;            /* the filter's 16-byte records (rtx_launch_denoise) */
+	DevBuf<float4> d_dn_feat;            /* the host-buffer calls' device copies */
+	DevBuf<float> d_dn_rgb;
+	DevBuf<unsigned long long> d_dn_ctr; /* k_dn_pack's hit-pixel count */
 	rtx_denoise_stats dn_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
@@ -241,5 +306,78 @@ uint32_t rtx_wide8_build(const std::vector<DNode> &inner, uint32_t nnodes, const
 			 double fpad, QFrame &F, bool &skipped, std::vector<DW8> &out, std::vector<uint32_t> &leafmap);
 /* one frame (or tile shard) into device buffers on stream */
 int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z, hipStream_t stream);
+/* rtx_scene.cpp: c's scene buffers freed (c's device current) */
+RTX_HIDDEN void rtx_free_scene(rtx_ctx *c);
+/* rtx_query.cpp: n checked rays on device buffers into c->ray_stats (the feature buffers' query too) */
+RTX_HIDDEN int rtx_rays_common(rtx_ctx *c, uint32_t n, const void *d_rays, void *d_hits, uint32_t flags, hipStream_t stream);
+
+/* Steps that more than one entry point takes.  They return the HIP error and each caller reports it
+ * with its own code and text. */
+
+/* c->d_rgb and c->d_z with room for px pixels (rtx_render, rtx_postprocess, rtx_group_render) */
+static inline hipError_t rtx_ensure_framebuffer(rtx_ctx *c, size_t px)
+{
+	const hipError_t e = c->d_rgb.grow(px * 3 * sizeof(float));
+	return e != hipSuccess ? e : c->d_z.grow(px * sizeof(float));
+}
+
+/* k_trace's and k_rays' lane-stack entries beyond the LDS part, [entry][grid lane], for a grid of
+ * `waves` waves on c's scene: the render sizes the buffer for its own waves, and a query may come
+ * first or run a larger grid */
+static inline hipError_t rtx_ensure_ostk(rtx_ctx *c, uint32_t waves)
+{
+	hipError_t e = hipSuccess;
+	if (c->scene.stack_size > RTX_TRACE_LSTK)
+		e = c->d_ostk.grow((size_t)waves * 64 * (c->scene.stack_size - RTX_TRACE_LSTK) * sizeof(uint32_t));
+	c->scene.ostk = c->d_ostk;
+	return e;
+}
+
+/* k_shadow's LDS stack size and spill area into S (c's scene for a render, which sets them at
+ * every render; a query's own copy, since a query may come first): 8-wide trees deeper than the
+ * LDS lane stacks spill the deeper entries of every lane of the largest k_shadow grid (one group
+ * per level at most).  A caller that reports a failed allocation in its own way learns of one through
+ * *alloc (false: the grid-size query failed). */
+static inline hipError_t rtx_ensure_w8spill(rtx_ctx *c, DScene &S, bool *alloc = nullptr)
+{
+	if (alloc)
+		*alloc = false;
+	S.w8lstk = c->opt_lstk;
+	S.w8spill = nullptr;
+	S.w8spill_lanes = 0;
+	if (!(S.w8 && S.w8depth > S.w8lstk + 1))
+		return hipSuccess;
+	uint32_t lanes = 0;
+	hipError_t e = rtx_shadow_grid_lanes((uint32_t)c->cus, &lanes);
+	if (e != hipSuccess)
+		return e;
+	if (alloc)
+		*alloc = true;
+	e = c->d_w8spill.grow((size_t)lanes * (S.w8depth - 1 - S.w8lstk) * sizeof(uint32_t));
+	if (e != hipSuccess)
+		return e;
+	S.w8spill = c->d_w8spill;
+	S.w8spill_lanes = lanes;
+	return hipSuccess;
+}
+
+/* the queries' counters (c->d_rctr), allocated at the first query and zeroed on stream */
+static inline hipError_t rtx_reset_query_counters(rtx_ctx *c, hipStream_t stream)
+{
+	const hipError_t e = c->d_rctr.grow(sizeof(unsigned long long) * RTX_RQ_N);
+	return e != hipSuccess ? e : hipMemsetAsync(c->d_rctr, 0, sizeof(unsigned long long) * RTX_RQ_N, stream);
+}
+
+static inline DFrame rtx_dframe(const rtx_frame *fr)
+{
+	DFrame F;
+	F.width = fr->width;
+	F.height = fr->height;
+	memcpy(F.corner, fr->corner, 12);
+	memcpy(F.step_x, fr->step_x, 12);
+	memcpy(F.step_y, fr->step_y, 12);
+	memcpy(F.origin, fr->origin, 12);
+	return F;
+}
 
 #endif

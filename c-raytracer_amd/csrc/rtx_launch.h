@@ -1,0 +1,115 @@
+/*
+ * The host entry points of the library's device files, declared once: every extern "C" launcher,
+ * code-object loader and size / occupancy query a .hip file defines.  The host callers include it,
+ * and so does each .hip file for its own definitions, so a definition that drifts from its
+ * declaration does not compile (C linkage alone would link it).
+ *
+ * The functions take the D* records (rtx_device.h) by pointer only, so they are forward-declared
+ * here and a device file includes nothing it did not include before.
+ */
+#ifndef RTX_LAUNCH_H
+#define RTX_LAUNCH_H
+
+#include <hip/hip_runtime.h>
+
+#include "rtx.h"
+
+struct DNode;
+struct DPrim;
+struct DW8;
+struct DW8S;
+struct DMaterial;
+struct DScene;
+struct DFrame;
+struct DParams;
+struct DTask;
+
+#define RTX_HIDDEN __attribute__((visibility("hidden")))
+
+extern "C" {
+
+/* rtx_build.hip: the BVH2 builders on the device */
+hipError_t rtx_lbvh_build(uint32_t n, const float *d_lo, const float *d_hi, const DPrim *d_prims_in, const float blo[3],
+			  const float bhi[3], uint32_t max_leaf, DNode **recs_out, uint32_t *nnodes_out, uint32_t *root_out,
+			  uint32_t *depth_out, hipStream_t st);
+hipError_t rtx_ploc_build(uint32_t n, const float *d_lo, const float *d_hi, const DPrim *d_prims_in, const float blo[3],
+			  const float bhi[3], uint32_t max_leaf, DNode **recs_out, uint32_t *nnodes_out, uint32_t *root_out,
+			  uint32_t *depth_out, uint32_t *rounds_out, hipStream_t st);
+hipError_t rtx_sah_build(uint32_t n, const float *d_lo, const float *d_hi, const DPrim *d_prims_in, uint32_t max_leaf,
+			 uint32_t bins, uint32_t max_depth, float c_trav, float c_isect, DNode **recs_out, uint32_t *nnodes_out,
+			 uint32_t *root_out, uint32_t *depth_out, uint32_t *levels_out, hipStream_t st);
+hipError_t rtx_launch_find_prims(const DPrim *prims, uint32_t n, const uint32_t *objs, uint32_t nobj, uint32_t *out,
+				 hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_build(void);
+
+/* rtx_wide8_dev.hip: the 8-wide tree collapsed on the device */
+hipError_t rtx_launch_w8_scalar(uint32_t n, const DW8 *w8, const uint32_t *leafmap, DW8S *w8s, hipStream_t st);
+hipError_t rtx_w8_collapse_device(const DNode *recs, uint32_t nnodes, uint32_t nb, const uint32_t *skip_obj,
+				  uint32_t num_objects, DW8 **w8_out, DW8S **w8s_out, uint32_t **leafmap_out,
+				  uint32_t *entries_out, uint32_t *scalar_entries_out, uint32_t *depth_out, uint32_t *wide_out,
+				  uint32_t *top_out, float qo[3], float qs[3], hipStream_t st);
+RTX_HIDDEN hipError_t rtx_load_wide8_dev(void);
+
+/* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays */
+size_t rtx_trace_lds_bytes(uint32_t stack_size);
+hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu);
+hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const DParams *P, float *rgb, float *z, DTask *tasks,
+			    uint32_t task_cap, float4 *staging, uint32_t staging_cap, float4 *sp_out, uint32_t sp_cap,
+			    uint2 *tile_rec, uint32_t tile_begin, uint32_t tile_end, unsigned long long *ctr, uint32_t waves,
+			    int count, hipStream_t stream);
+hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec, const float4 *contrib,
+			    uint32_t tile_begin, uint32_t ntiles, float *rgb, hipStream_t stream);
+size_t rtx_rays_lds_bytes(uint32_t stack_size);
+hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu);
+hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
+			   uint32_t queues, uint32_t grab, unsigned long long *ctr, uint32_t waves, int count, int any,
+			   hipStream_t stream);
+hipError_t rtx_launch_frame_rays(const DFrame *F, float4 *rays, hipStream_t stream);
+hipError_t rtx_launch_kat(int kind, uint32_t n, const float *in, float *out, int u32mode, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_trace(void);
+
+/* rtx_shadow.hip: k_shadow, k_point_masks, k_shadow_rays, the 8-wide tree's leaf fill */
+hipError_t rtx_launch_w8_fill(const DPrim *prims, const DMaterial *mats, const uint32_t *leafmap, uint32_t n, DW8 *out,
+			      hipStream_t stream);
+hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *in, float *out, hipStream_t stream);
+hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes);
+hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm, uint32_t n_sp,
+			     uint32_t per_wave, uint32_t slot_b, float4 *contrib, unsigned long long *ctr, int count,
+			     uint32_t cus, hipStream_t stream, uint32_t *pmask, int *premasked);
+hipError_t rtx_launch_shadow_rays(const DScene *S, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
+				  int slots, int count, uint32_t cus, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_shadow(void);
+
+/* rtx_sort.hip: the shade points' and the query rays' Morton sorts */
+hipError_t rtx_spsort_temp_bytes(uint32_t n, size_t *bytes);
+hipError_t rtx_launch_spsort(const float4 *sp, uint32_t n, const float lo[3], const float hi[3], uint32_t *keys0,
+			     uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp, size_t temp_bytes,
+			     const uint32_t **perm, hipStream_t stream);
+hipError_t rtx_raysort_temp_bytes(uint32_t n, size_t *bytes);
+hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const float lo[3], const float hi[3], uint32_t *keys0,
+			      uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp, size_t temp_bytes,
+			      const uint32_t **perm, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_sort(void);
+
+/* rtx_post.hip */
+hipError_t rtx_launch_post(uint32_t w, uint32_t h, const rtx_post *pp, float *rgb, const float *z, int *rad, float4 *pv,
+			   unsigned *scratch, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_post(void);
+
+/* rtx_gather.hip: a device group's tile records */
+hipError_t rtx_launch_tile_pack(const float *rgb, const float *z, uint32_t w, uint32_t h, uint32_t off, uint32_t stride,
+				float4 *out, hipStream_t stream);
+hipError_t rtx_launch_tile_unpack(const float4 *in, uint32_t w, uint32_t h, uint32_t off, uint32_t stride, float *rgb,
+				  float *z, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_gather(void);
+
+/* rtx_denoise.hip */
+RTX_HIDDEN hipError_t rtx_launch_dn_features(uint64_t n, const float4 *rays, const float4 *hits, const DMaterial *mats,
+					     int u32conv, float4 *out, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_denoise(uint32_t w, uint32_t h, const rtx_denoise_params *dp, const float4 *feat,
+					 float *rgb, float4 *work, unsigned long long *hit_count, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_denoise(void);
+
+}
+
+#endif

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "rtx.h"
+#include "rtx_launch.h"
 
 __global__ __launch_bounds__(256) void k_post_prep(uint32_t n, float *__restrict__ rgb, const float *__restrict__ z,
 						   int brighten, float factor, int dof, float scale, float bias,

@@ -1,6 +1,6 @@
 /*
  * Quantisation of the threaded BVH's boxes (rtx_device.h DQNode), shared by the uploader
- * (rtx_api.cpp) and the device KAT of the quantised box test (rtx_shadow.hip), so the KAT
+ * (rtx_scene.cpp) and the device KAT of the quantised box test (rtx_shadow.hip), so the KAT
  * tests exactly the boxes the walk reads.  Compiled by hipcc only.
  *
  * A plane pair (lo, hi) on one axis of the frame (qo, qs) becomes 16-bit integers
@@ -34,7 +34,7 @@ __host__ __device__ static inline uint32_t rtx_quantise8(uint32_t q16, uint32_t 
 
 /* The bounding sphere {centre, radius} of a record k_shadow tests one by one (rtx_device.h
  * DEmitter: a sphere itself, a triangle's circumscribing sphere about its centroid), formed in
- * double and padded like the cone cull's tree spheres (rtx_api.cpp build_cull) for the kernel's
+ * double and padded like the cone cull's tree spheres (rtx_upload.cpp build_cull) for the kernel's
  * float test (rtx_shadow.hip point_masks). */
 __host__ __device__ static inline void rtx_record_sphere(bool sphere, const float *p0, const float *p1, const float *p2, float radius,
 							 float out[4])

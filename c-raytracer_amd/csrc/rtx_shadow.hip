@@ -39,6 +39,7 @@
 #include "rtx_quant.h"
 #include "rtx_wave.h"
 #include "rtx_w8.h"
+#include "rtx_launch.h"
 
 #ifndef RTX_DEBUG_NOWALK
 #define RTX_DEBUG_NOWALK 0 /* measurement only: skip the BVH walk (everything else in k_shadow stays) */
@@ -936,7 +937,7 @@ __device__ __forceinline__ f3 shade_terms(int32_t att, int32_t refl, f3 n, f3 di
  * a point without diffuse colour, and a specular factor of 0 (pw == 0: ks aside, specular_mul
  * <= 0 under an odd or non-integer shininess) or a material without ks.  The products must stay
  * finite, or a 0 factor would give NaN, not 0: kd li' and ks li' (li' = li attf) are finite
- * here, and with a transmittance T, |T| <= 1 (the scene's flag, rtx_api.cpp scene_dark_ok),
+ * here, and with a transmittance T, |T| <= 1 (the scene's flag, rtx_upload.cpp scene_dark_ok),
  * |fl(fl(li T) attf)| <= |fl(li attf)| as rounding is monotonic, so the products formed after
  * a walk are no larger.  The lanes' pw is formed only when some lane passed the diffuse part
  * (a lit point's packets pay the dot product alone).  (KAT: RTX_KAT_DARK) */
@@ -2161,7 +2162,7 @@ extern "C" hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *i
 }
 
 /* ------------------------------------------------------------------------ */
-/* launcher (called from rtx_api.cpp)                                       */
+/* launcher (declared in rtx_launch.h)                                      */
 /* ------------------------------------------------------------------------ */
 template <bool C, int O, int W, int P> static hipError_t shadow_slots(uint32_t cus, uint32_t *slots)
 {

@@ -16,6 +16,8 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "rtx_launch.h"
+
 #define SPREC 6 /* float4 per shade-point record (rtx_kernels.hip) */
 
 __device__ __forceinline__ uint32_t spread10(uint32_t v)

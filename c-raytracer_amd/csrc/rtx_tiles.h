@@ -1,6 +1,6 @@
 /*
  * Tile sharding and the packed tile records of the multi-device gather (rtx_group_render),
- * shared by the host reference (rtx_api.cpp rtx_tile_pack_host) and the device kernels
+ * shared by the host reference (rtx_group.cpp rtx_tile_pack_host) and the device kernels
  * (rtx_gather.hip), so both index pixels identically.
  *
  * A frame is cut into 8x8-pixel tiles, row-major (render.c:349-352 walks rows; the tiles are

@@ -31,6 +31,7 @@
 #include "rtx_kat.h"
 #include "rtx_wave.h"
 #include "rtx_w8.h"
+#include "rtx_launch.h"
 
 /* ------------------------------------------------------------------------ */
 /* closest hit: inside-object shortcut, planes, then BVH (render.c:118-147)  */
@@ -1160,7 +1161,7 @@ __global__ void k_kat(int kind, uint32_t n, const float *__restrict__ in, float 
 }
 
 /* ------------------------------------------------------------------------ */
-/* launchers (called from rtx_api.cpp)                                      */
+/* launchers (declared in rtx_launch.h)                                     */
 /* ------------------------------------------------------------------------ */
 extern "C" size_t rtx_trace_lds_bytes(uint32_t stack_size)
 {

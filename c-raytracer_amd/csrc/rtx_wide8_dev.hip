@@ -16,7 +16,7 @@
  *                 children for the next level (their entry blocks follow in level order)
  *   k_w8d_scalar  the scalar-path copies (DW8S) of the inner entries
  * Levels are laid out breadth-first (the host collapse: depth-first); the walk reads either.
- * Single-primitive BVH2 leaves only (the default RTX_OPT_BVH_LEAF 1); rtx_api.cpp keeps the
+ * Single-primitive BVH2 leaves only (the default RTX_OPT_BVH_LEAF 1); rtx_scene.cpp keeps the
  * host collapse for larger leaves.
  */
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@
 #include "rtx.h"
 #include "rtx_device.h"
 #include "rtx_quant.h"
+#include "rtx_launch.h"
 
 #ifndef RTX_W8_C_PRIM
 #define RTX_W8_C_PRIM 0.3f

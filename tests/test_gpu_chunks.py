@@ -1,4 +1,4 @@
-"""A render in several chunks (rtx_api.cpp rtx_render_common) is the one-chunk render, bit for bit.
+"""A render in several chunks (rtx_render.cpp rtx_render_common) is the one-chunk render, bit for bit.
 
 A frame's 8x8 tiles are traced, lit and accumulated chunk by chunk: the shade-point buffers are
 sized for a chunk from an estimate of shade points per tile, and a chunk whose shade points

@@ -1,4 +1,4 @@
-"""k_shadow's cone cull (rtx.h RTX_OPT_SHADOW_CULL, rtx_shadow.hip cone_clear, rtx_api.cpp
+"""k_shadow's cone cull (rtx.h RTX_OPT_SHADOW_CULL, rtx_shadow.hip cone_clear, rtx_upload.cpp
 build_cull): a packet of one shade point's samples of one emitter skips the 8-wide walk when the
 cone from the point around the emitter's bounding sphere meets none of the bounding spheres of the
 tree's second level.  Every shadow ray of the packet lies in that cone, so a skipped walk is one

@@ -1,7 +1,7 @@
 """k_shadow's per-point masks (rtx.h RTX_OPT_SHADOW_POINT, rtx_shadow.hip point_masks / clear_run):
 a shade point with 64 light samples or more decides once, per emitter, that no ray from it to the
 emitter can meet a plane (plane_clear) or an object tested one by one (the cone test against the
-records' bounding spheres, rtx_api.cpp build_lsph); its packets skip those tests, and a point clear
+records' bounding spheres, rtx_upload.cpp build_lsph); its packets skip those tests, and a point clear
 of the tree, the planes and the records runs its packets without any shadow query.
 
  1. soundness: over seeded cases, no (point, light, plane / record) has its clear bit set together
