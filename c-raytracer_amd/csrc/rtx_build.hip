@@ -405,6 +405,13 @@ __global__ __launch_bounds__(PLOC_T) void k_pl_init(uint32_t n, const uint32_t *
 	cl[q] = q;
 }
 
+/* the order of pairs (i, j) of equal distance (k_pl_nn): parity of the lower index, then |i - j|, then the lower index */
+__device__ __forceinline__ uint64_t pl_tie_key(int i, int j)
+{
+	const uint32_t m = (uint32_t)min(i, j), w = (uint32_t)abs(i - j);
+	return ((uint64_t)(m & 1u) << 40) | ((uint64_t)w << 32) | m;
+}
+
 /* nearest neighbour of each cluster within the radius (boxes staged through LDS) */
 __global__ __launch_bounds__(PLOC_T) void k_pl_nn(uint32_t m, const float *__restrict__ cb, uint32_t *__restrict__ nn)
 {
@@ -432,9 +439,12 @@ __global__ __launch_bounds__(PLOC_T) void k_pl_nn(uint32_t m, const float *__res
 			u[3 + a] = fmaxf(sb[li][3 + a], sb[li + o][3 + a]);
 		}
 		const float d = box_area6(u);
-		/* pair order (d, lower index, higher index): for a fixed i the lower index decides ties
-		 * among j < i by j, and any j < i before any j > i */
-		if (d < bd || (d == bd && j < bj)) {
+		/* pair order (d, parity of the lower index, distance, lower index): a key of the pair alone and
+		 * unique to it, so the order is total and the least pair is mutual.  Among ties an even lower
+		 * index comes first, then the nearer neighbour: coincident boxes (every pair ties) merge as
+		 * (0, 1), (2, 3), ... and halve each round, where ties by the lower index alone merged one pair
+		 * a round into a chain */
+		if (d < bd || (d == bd && pl_tie_key(i, j) < pl_tie_key(i, bj))) {
 			bd = d;
 			bj = j;
 		}

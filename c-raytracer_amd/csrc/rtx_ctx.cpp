@@ -249,6 +249,33 @@ extern "C" int rtx_read_wide_tree(rtx_ctx *c, void *entries, uint32_t capacity, 
 	return RTX_OK;
 }
 
+extern "C" int rtx_read_bvh2(rtx_ctx *c, void *records, uint32_t record_capacity, uint32_t *num_nodes, uint32_t *num_prims,
+			     uint32_t *root_ref, void *qnodes, uint32_t qnode_capacity, uint32_t *num_qnodes, float qframe[6])
+{
+	if (!c || !num_nodes || !num_prims || !root_ref || !num_qnodes)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (!c->have_scene)
+		return fail(RTX_ERR_STATE, "rtx_read_bvh2 before rtx_upload_scene");
+	const DScene &S = c->scene;
+	*num_nodes = S.num_nodes;
+	*num_prims = S.num_prims;
+	*root_ref = S.root_ref;
+	*num_qnodes = S.qnodes ? S.num_qnodes : 0u;
+	if (qframe) {
+		memcpy(qframe, S.qo, 12);
+		memcpy(qframe + 3, S.qs, 12);
+	}
+	const uint64_t nrec = std::min<uint64_t>(record_capacity, (uint64_t)S.num_nodes + S.num_prims);
+	const uint32_t nq = std::min(qnode_capacity, *num_qnodes);
+	if ((records && nrec) || (qnodes && nq))
+		HIP_TRY(hipSetDevice(c->device));
+	if (records && nrec)
+		HIP_TRY(hipMemcpy(records, S.nodes, (size_t)nrec * sizeof(DNode), hipMemcpyDeviceToHost));
+	if (qnodes && nq)
+		HIP_TRY(hipMemcpy(qnodes, S.qnodes, (size_t)nq * sizeof(DQNode), hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
 /* the statistics getters: a copy of one of the context's records */
 template <class T> static int get_stats(const rtx_ctx *c, T rtx_ctx::*rec, T *out)
 {

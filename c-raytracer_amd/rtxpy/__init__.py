@@ -276,6 +276,21 @@ class Renderer:
             _check(self.lib.rtx_read_wide_tree(self._ctx, ent.ctypes.data, n.value, C.byref(n), frame.ctypes.data))
         return ent, frame
 
+    def bvh2(self):
+        """the uploaded BVH2 (rtx_read_bvh2), a dict: nodes uint32 (nnodes, 16) and prims uint32 (nprims, 16), the
+        64-byte DNode / DPrim records of csrc/rtx_device.h as words (view as float32 for the boxes), root_ref,
+        qnodes uint32 (nq, 4), the threaded 16-bit copy (nq = 0: the context holds none), qframe float32 (6,)"""
+        nn, nb, root, nq = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        qframe = np.zeros(6, np.float32)
+        _check(self.lib.rtx_read_bvh2(self._ctx, None, 0, C.byref(nn), C.byref(nb), C.byref(root), None, 0, C.byref(nq),
+                                      qframe.ctypes.data))
+        rec = np.zeros((nn.value + nb.value, 16), np.uint32)
+        qn = np.zeros((nq.value, 4), np.uint32)
+        if len(rec) or len(qn):
+            _check(self.lib.rtx_read_bvh2(self._ctx, rec.ctypes.data, len(rec), C.byref(nn), C.byref(nb), C.byref(root),
+                                          qn.ctypes.data, len(qn), C.byref(nq), qframe.ctypes.data))
+        return {"nodes": rec[:nn.value], "prims": rec[nn.value:], "root_ref": root.value, "qnodes": qn, "qframe": qframe}
+
     def stats(self):
         s = Stats()
         _check(self.lib.rtx_get_stats(self._ctx, C.byref(s)))

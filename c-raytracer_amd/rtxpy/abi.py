@@ -204,7 +204,7 @@ KAT_NAMES = ["moller", "sphere", "plane", "slab", "noise", "texture", "sph_light
 # symbols include/rtx.h declares (checked by tests/test_abi.py)
 RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload_scene", "rtx_render",
                "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_premask_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
-               "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree",
+               "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree", "rtx_read_bvh2",
                "rtx_group_set_builder", "rtx_group_set_option", "rtx_group_upload_scene", "rtx_group_render", "rtx_group_get_stats", "rtx_group_device_stats",
                "rtx_group_get_point_stats", "rtx_group_device_point_stats",
                "rtx_group_get_dark_stats", "rtx_group_device_dark_stats",
@@ -297,6 +297,9 @@ def declare_rtx(lib):
     lib.rtx_group_open.restype = C.c_int
     lib.rtx_read_wide_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
     lib.rtx_read_wide_tree.restype = C.c_int
+    lib.rtx_read_bvh2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+    lib.rtx_read_bvh2.restype = C.c_int
     lib.rtx_group_open_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.rtx_group_open_loopback.restype = C.c_int
     lib.rtx_group_open_rccl_self.argtypes = [C.c_int, C.POINTER(C.c_void_p)]

@@ -370,6 +370,14 @@ const char *rtx_last_error(void);
  * host memory, at most `capacity` of them; *count = the tree's entry count (0: no 8-wide tree),
  * frame[6] = its 16-bit frame (origin, scale per axis).  entries may be NULL to query the count. */
 int rtx_read_wide_tree(rtx_ctx *ctx, void *entries, uint32_t capacity, uint32_t *count, float frame[6]);
+/* Diagnostics (tests): the uploaded BVH2.  records: its 64-byte records (csrc/rtx_device.h), *num_nodes DNode
+ * inner nodes followed by *num_prims DPrim primitive records in leaf order, at most record_capacity of them;
+ * *root_ref = the root's ref (RTX_EMPTY_REF 0xFFFFFFFF: no bounded objects).  qnodes: the threaded 16-bit copy's
+ * 16-byte DQNode records, at most qnode_capacity of them; *num_qnodes = their count (0: the context holds no
+ * threaded copy, as when the shadow walk takes the 8-wide tree or no tree), qframe[6] = its 16-bit frame (origin,
+ * scale per axis).  records, qnodes and qframe may be NULL to query the counts. */
+int rtx_read_bvh2(rtx_ctx *ctx, void *records, uint32_t record_capacity, uint32_t *num_nodes, uint32_t *num_prims,
+		  uint32_t *root_ref, void *qnodes, uint32_t qnode_capacity, uint32_t *num_qnodes, float qframe[6]);
 
 /*
  * Ray queries: the closest hit (or any hit) of a caller's own rays against the uploaded scene,

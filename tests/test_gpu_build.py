@@ -158,32 +158,7 @@ def test_gpu_wave_counts_vary_only_with_packing(renderer, name):
         assert abs(x - y) <= 0.01 * max(x, y, 1), (name, f, x, y)
 
 
-def wide_tree_diff(ta, tb):
-    """walk two 8-wide trees (rtx_read_wide_tree entries) from their roots in step and list where
-    they differ: node words other than the child base (the layouts differ: host depth-first, device
-    breadth-first), and the leaf entries (primitive record copies)"""
-    names = ["w0 origin", "w1 origin/steps", "w2 inner mask", "w3 child/transparent masks"] + \
-        [f"w{k} planes" for k in range(4, 16)]
-    diffs = []
-    q = [(0, 0, True)]
-    while q:
-        a, b, inner = q.pop()
-        ea, eb = ta[a], tb[b]
-        if not inner:  # leaf entries: the primitive record copies
-            if not np.array_equal(ea, eb):
-                diffs.append(("leaf", a, b, [k for k in range(16) if ea[k] != eb[k]]))
-            continue
-        wa, wb = ea.copy(), eb.copy()
-        wa[2] &= 0xFF
-        wb[2] &= 0xFF
-        if not np.array_equal(wa, wb):
-            diffs.append(("node", a, b, [names[k] for k in range(16) if wa[k] != wb[k]]))
-            continue
-        ba, bb = int(ea[2]) >> 8, int(eb[2]) >> 8
-        for c in range(8):
-            if (int(ea[3]) >> c) & 1:
-                q.append((ba + c, bb + c, bool((int(ea[2]) >> c) & 1)))
-    return diffs
+from tree_audit import wide_tree_diff  # noqa: E402  (the walk of two 8-wide trees in step)
 
 
 @pytest.mark.parametrize("name", ["s5_path2", "s6_amb", "s3_path2", "st_amb"])
