@@ -221,6 +221,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow dark samples %lld is not 0 or 1", (long long)value);
 		c->opt_dark = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_ORDER:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow sample order %lld is not 0 or 1", (long long)value);
+		c->opt_order = (int)value;
+		return RTX_OK;
 	case RTX_OPT_SHADOW_PREMASK:
 		if (value < 0 || value > 1)
 			return fail(RTX_ERR_ARG, "shadow pre-mask %lld is not 0 or 1", (long long)value);
@@ -288,6 +293,7 @@ template <class T> static int get_stats(const rtx_ctx *c, T rtx_ctx::*rec, T *ou
 extern "C" int rtx_get_stats(const rtx_ctx *c, rtx_stats *out) { return get_stats(c, &rtx_ctx::stats, out); }
 extern "C" int rtx_get_point_stats(const rtx_ctx *c, rtx_point_stats *out) { return get_stats(c, &rtx_ctx::pstats, out); }
 extern "C" int rtx_get_dark_stats(const rtx_ctx *c, rtx_dark_stats *out) { return get_stats(c, &rtx_ctx::dstats, out); }
+extern "C" int rtx_get_order_stats(const rtx_ctx *c, rtx_order_stats *out) { return get_stats(c, &rtx_ctx::ostats, out); }
 extern "C" int rtx_get_premask_stats(const rtx_ctx *c, rtx_premask_stats *out) { return get_stats(c, &rtx_ctx::mstats, out); }
 extern "C" int rtx_get_ray_stats(const rtx_ctx *c, rtx_ray_stats *out) { return get_stats(c, &rtx_ctx::ray_stats, out); }
 extern "C" int rtx_get_shadow_ray_stats(const rtx_ctx *c, rtx_shadow_ray_stats *out)

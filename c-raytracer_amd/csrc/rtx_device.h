@@ -270,7 +270,14 @@ typedef struct DScene {
 	                        * a light sample whose terms are 0 stays 0 under any transmittance a walk gathers */
 	uint32_t dark;         /* RTX_OPT_SHADOW_DARK (and RTX_OPT_SHADOW_CULL not 0): such samples skip their shadow
 	                        * query on the wave-uniform path (rtx_shadow.hip sample_dark) */
+	uint32_t order;        /* RTX_OPT_SHADOW_ORDER: a walking point's light samples are walked in the order of their
+	                        * light points across the cone (rtx_shadow.hip order_begin) */
+	uint32_t *ordbuf;      /* ... the waves' order / result slices, RTX_ORD_WORDS words per grid wave */
+	uint32_t ordbuf_waves; /* grid waves the buffer was sized for (0: none) */
 } DScene;
+#define RTX_ORD_CAP 1024u                /* most samples of one emitter a point orders */
+#define RTX_ORD_BUCKETS 16u              /* buckets of the key */
+#define RTX_ORD_WORDS (4u * RTX_ORD_CAP) /* a wave's slice: order[CAP], then the results' x, y and z, CAP floats each */
 #define RTX_CULL_MAX 64
 
 /* k_trace keeps the first RTX_TRACE_LSTK entries of a lane's closest-hit stack in LDS and the
@@ -345,6 +352,8 @@ enum {
 	RTX_C_SDARK,        /* count mode: dark shadow rays answered without a query (sample_dark; packets the cone
 	                     * cull cleared are not looked at) */
 	RTX_C_SDARKPK,      /* count mode: ... of which in packets of dark rays alone */
+	RTX_C_SORDPT,       /* count mode: runs of one emitter's samples of a point walked in key order (order_begin) */
+	RTX_C_SORDRAY,      /* count mode: ... the shadow rays in them (the dark ones are not) */
 	RTX_C_N
 };
 

@@ -62,6 +62,7 @@ struct rtx_group {
 	rtx_stats stats{};
 	rtx_point_stats pstats{};
 	rtx_dark_stats dstats{};
+	rtx_order_stats ostats{};
 	rtx_premask_stats mstats{};
 };
 
@@ -482,6 +483,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	rtx_stats s = c0->stats;
 	rtx_point_stats ps = c0->pstats;
 	rtx_dark_stats ds = c0->dstats;
+	rtx_order_stats os = c0->ostats;
 	rtx_premask_stats ms = c0->mstats;
 	for (int r = 1; r < n; r++) {
 		const rtx_stats &o = g->ctx[r]->stats;
@@ -511,6 +513,8 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 		ps.shadow_point_clear += g->ctx[r]->pstats.shadow_point_clear;
 		ds.shadow_dark_rays += g->ctx[r]->dstats.shadow_dark_rays;
 		ds.shadow_dark_packet_rays += g->ctx[r]->dstats.shadow_dark_packet_rays;
+		os.shadow_ordered_points += g->ctx[r]->ostats.shadow_ordered_points;
+		os.shadow_ordered_rays += g->ctx[r]->ostats.shadow_ordered_rays;
 		ms.premask_points += g->ctx[r]->mstats.premask_points;
 		s.waves += o.waves;
 		s.chunks += o.chunks;
@@ -527,6 +531,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	g->stats = s;
 	g->pstats = ps;
 	g->dstats = ds;
+	g->ostats = os;
 	g->mstats = ms;
 	return RTX_OK;
 }
@@ -572,6 +577,24 @@ extern "C" int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_s
 	if (r < 0 || r >= g->n)
 		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
 	*out = g->ctx[r]->dstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_get_order_stats(const rtx_group *g, rtx_order_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = g->ostats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_device_order_stats(const rtx_group *g, int r, rtx_order_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (r < 0 || r >= g->n)
+		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
+	*out = g->ctx[r]->ostats;
 	return RTX_OK;
 }
 

@@ -175,6 +175,7 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float4> d_staging;
 	DevBuf<float4> d_sp;
 	DevBuf<float4> d_contrib;
+	DevBuf<uint32_t> d_ordbuf; /* k_shadow's order / result slices, RTX_ORD_WORDS words per grid wave (DScene.ordbuf) */
 	DevBuf<uint32_t> d_pmask; /* the chunk's per-point masks, a word per record (k_point_masks) */
 	DevBuf<uint2> d_tile_rec;
 	/* shade points per tile seen by the last render of this scene with the same GI / bounce
@@ -193,6 +194,7 @@ struct rtx_ctx : CtxHandles {
 	rtx_stats stats{};
 	rtx_point_stats pstats{}; /* rtx_get_point_stats */
 	rtx_dark_stats dstats{};  /* rtx_get_dark_stats */
+	rtx_order_stats ostats{}; /* rtx_get_order_stats */
 	rtx_premask_stats mstats{}; /* rtx_get_premask_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
 	DevBuf<unsigned long long> d_rctr;
@@ -222,6 +224,7 @@ struct rtx_ctx : CtxHandles {
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
 	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	int opt_dark = 1;         /* RTX_OPT_SHADOW_DARK: light samples that add nothing skip their shadow query */
+	int opt_order = 1;        /* RTX_OPT_SHADOW_ORDER: a walking point's light samples walked in key order */
 	int opt_premask = 1;      /* RTX_OPT_SHADOW_PREMASK: the per-point masks formed before k_shadow, one point per lane */
 	uint32_t mem_share = 1;  /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */

@@ -185,6 +185,18 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		Ssh.cull_slots = c->opt_cull == 2 ? 1u : 0u;
 		Ssh.point = (c->opt_cull && c->opt_point) ? 1u : 0u; /* RTX_OPT_SHADOW_POINT */
 		Ssh.dark = (c->opt_cull && c->opt_dark) ? 1u : 0u;   /* RTX_OPT_SHADOW_DARK */
+		/* RTX_OPT_SHADOW_ORDER: wave-uniform packets that walk a tree, the waves' slices for the largest grid */
+		Ssh.order = 0u;
+		Ssh.ordbuf = nullptr;
+		Ssh.ordbuf_waves = 0u;
+		if (c->opt_order && slot_b == 64 && Ssh.root_ref != RTX_EMPTY_REF && !Ssh.lin) {
+			uint32_t lanes = 0;
+			HIP_TRY(rtx_shadow_grid_lanes((uint32_t)c->cus, &lanes));
+			HIP_TRY(c->d_ordbuf.grow((size_t)(lanes / 64) * RTX_ORD_WORDS * sizeof(uint32_t)));
+			Ssh.order = 1u;
+			Ssh.ordbuf = c->d_ordbuf;
+			Ssh.ordbuf_waves = lanes / 64;
+		}
 		int premasked = 0; /* RTX_OPT_SHADOW_PREMASK: k_point_masks ran for this chunk */
 		HIP_TRY(rtx_launch_shadow(&Ssh, &P, c->d_sp, perm, n_sp, per_wave, slot_b, c->d_contrib, c->d_ctr,
 					  p->count_traversal, (uint32_t)c->cus, stream, c->opt_premask ? c->d_pmask : nullptr,
@@ -245,6 +257,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	c->pstats.shadow_point_clear = ctr[RTX_C_SPCLEAR];
 	c->dstats.shadow_dark_rays = ctr[RTX_C_SDARK];
 	c->dstats.shadow_dark_packet_rays = ctr[RTX_C_SDARKPK];
+	c->ostats.shadow_ordered_points = ctr[RTX_C_SORDPT];
+	c->ostats.shadow_ordered_rays = ctr[RTX_C_SORDRAY];
 	c->mstats.premask_points = premask_points;
 	st.node_visits = ctr[RTX_C_NODES] + st.shadow_node_visits;
 	st.tri_tests = ctr[RTX_C_TRIS] + ctr[RTX_C_STRIS];

@@ -173,6 +173,8 @@ struct ShadowCount {
 	u64 pclear;    /* rays of all-clear points (clear_run) */
 	u64 dark;      /* rays answered without a query: their sample adds nothing to the point (sample_dark) */
 	u64 dpack;     /* ... of which in packets whose every sample was dark (no shadow query at all) */
+	u64 ordpt;     /* runs of one emitter's samples of a point walked in key order (order_begin) */
+	u64 ordray;    /* ... the rays walked in them */
 };
 
 /* one primitive record (a, b, c = its first 48 bytes) against this lane's shadow ray
@@ -483,14 +485,16 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 				if (!(w.tgrp & 0xFFu))
 					w.tgrp = w.tn ? tq[--w.tn * WAVE + W8_LN] : 0u;
 			}
+			/* not counted here: a deferred test counts where its leaf is queued (below) */
+			uint32_t n0 = 0, n1 = 0;
 			if (!RTX_W8_TRIONLY || Q.sph) {
-				w8_defer_test<COUNT, true>(pr, o, d, tl, li, c.ntri, c.nsph);
+				w8_defer_test<false, true>(pr, o, d, tl, li, n0, n1);
 				if (RTX_W8_DEFER2 && pr2)
-					w8_defer_test<COUNT, true>(pr2, o, d, tl, li, c.ntri, c.nsph);
+					w8_defer_test<false, true>(pr2, o, d, tl, li, n0, n1);
 			} else {
-				w8_defer_test<COUNT, false>(pr, o, d, tl, li, c.ntri, c.nsph);
+				w8_defer_test<false, false>(pr, o, d, tl, li, n0, n1);
 				if (RTX_W8_DEFER2 && pr2)
-					w8_defer_test<COUNT, false>(pr2, o, d, tl, li, c.ntri, c.nsph);
+					w8_defer_test<false, false>(pr2, o, d, tl, li, n0, n1);
 			}
 		}
 		return;
@@ -536,6 +540,20 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 			c.nstep++;
 			c.nbox += popc64(v.nv);
 			c.nun += ballot(w.node != uni(w.node)) ? 0u : 1u;
+		}
+		if (COUNT) {
+			/* the transparent leaves' tests count here, where the ray's own walk calls for them (as a
+			 * ray walking alone tests them, in visit order, before a later opaque hit ends it): per-ray
+			 * work.  Counted where they run, the figure would follow the deferred rounds, which the
+			 * wave's lanes start together: a ray an opaque leaf blocks drops its queue, and how much of
+			 * it was tested by then depends on the rays that share its packet */
+			for (uint32_t m = dm; m; m &= m - 1) {
+				const char *pr = (const char *)(Q.w8 + base + (__builtin_ctz(m) ^ K));
+				if ((!RTX_W8_TRIONLY || Q.sph) && (__float_as_uint(ldg4(pr, 32).w) >> 24) == RTX_SPHERE)
+					c.nsph++;
+				else
+					c.ntri++;
+			}
 		}
 		if (dm) { /* transparent leaves: deferred */
 			const uint32_t g = (base << 8) | dm;
@@ -785,7 +803,8 @@ __device__ __forceinline__ bool shadow_query(const QBvh &Q, const char *__restri
 /* k_shadow arguments.  Lane 0 copies them to LDS; the loops re-read them from there behind a
  * compiler memory barrier, so none stays live in registers across the walk. */
 struct KShadow {
-	const DPrim *prims;   /* primitive records (DQNode leaf refs are byte offsets from `recs`) */
+	uint32_t *ord;        /* RTX_OPT_SHADOW_ORDER: the waves' order / result slices (DScene.ordbuf), RTX_ORD_WORDS
+	                       * words per grid wave; null: off, or the launch is not one it applies to */
 	const char *recs;     /* base of the record array the leaf refs point into */	const DQNode *qnodes; /* threaded quantised BVH */
 const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi are then its frame) */
 	const DW8S *w8s;      /* its nodes' scalar-path copies */
@@ -1539,6 +1558,153 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
 	return base;
 }
 
+/* The sample order of a walking point (RTX_OPT_SHADOW_ORDER).  A packet of 64 samples walks as long
+ * as its longest lane, and where a sample's light point lies across the cone from the shade point to
+ * the emitter predicts what its ray crosses: the occluder's silhouette cuts the emitter's disc.  So
+ * the samples [base, base + n) of one emitter, 64 < n <= RTX_ORD_CAP, every packet of them inside
+ * that emitter's samples, are walked in the order of a key: the bucket, of RTX_ORD_BUCKETS, of
+ * x = (lp - c) . b / lr, with (c, lr) the emitter's bounding sphere (emitter_sphere), lp the light
+ * point (p + ldist ldir; c - p is along the axis, so x = ldist (ldir . b) / lr) and b the unit
+ * vector across the cone axis toward the centre of the bounded objects' box (DTreeFrame c + cf; or, with that centre
+ * on the axis, across the world axis the cone axis is least along).  Dark samples (sample_dark)
+ * get no place in the order: they are never walked.
+ *   The key pass runs the packets in index order: each lane forms its sample as light_sample does
+ * (emitter_sample, sample_att, sample_dark: the same operations, so the same dark lanes), stores
+ * the bucket in its result slot and counts the buckets (lane b holds bucket b's count).  A second
+ * pass ranks every sample inside its bucket (ballot and mbcnt: stable in the index) and stores
+ * order[pos] = index - base, then zeroes the result slots.  The caller walks the packets of
+ * positions [64 k, 64 k + 64), stores each contribution at its sample's result slot and adds the
+ * slots in index order, lane l taking l, 64 + l, ..: the additions today's loop makes, in its order.
+ *   ob: the wave's slice of KShadow.ord.  Returns 0 (the run is not ordered: today's packets), or
+ * bit 31 | packets of the run << 16 | samples in the order.  (KAT: RTX_KAT_ORDER) */
+__device__ __forceinline__ uint32_t order_bucket(float x)
+{
+	const float v = floorf((x + 1.f) * (0.5f * (float)RTX_ORD_BUCKETS));
+	return (uint32_t)fminf(fmaxf(v, 0.f), (float)(RTX_ORD_BUCKETS - 1u)); /* NaN -> 0 */
+}
+/* the key's direction for the shade point p and the emitter sphere's centre lc */
+__device__ __forceinline__ f3 order_dir(f3 p, f3 lc, f3 tc)
+{
+	const f3 ax = sub3(lc, p), ref = sub3(tc, p);
+	const float aa = fmaxf(magsqr3(ax), 1e-37f);
+	f3 b = sub3(ref, mul3s(ax, dot3(ref, ax) / aa));
+	if (!(magsqr3(b) > 1e-8f * magsqr3(ref))) { /* the centre on the axis (or not finite) */
+		const float fx = fabsf(ax.x), fy = fabsf(ax.y), fz = fabsf(ax.z);
+		const f3 w = fx <= fy && fx <= fz ? mk3(1.f, 0.f, 0.f) : fy <= fz ? mk3(0.f, 1.f, 0.f) : mk3(0.f, 0.f, 1.f);
+		b = sub3(w, mul3s(ax, dot3(w, ax) / aa));
+	}
+	return mul3s(b, 1.f / sqrtf(fmaxf(magsqr3(b), 1e-37f)));
+}
+/* sample j of emitter number e (Eu) of the shade point `rec` at p, formed as light_sample forms it:
+ * its bucket, RTX_ORD_BUCKETS for a dark or idle one; *xo: the key's x */
+__device__ __forceinline__ uint32_t order_key(const KShadow &ks, const float4 *rec, const DEmitter &Eu, uint32_t e, uint32_t j, uint32_t ka,
+					      uint32_t kb, f3 p, f3 b, float ilr, bool dk_on, bool act, bool &dark, float *xo = nullptr)
+{
+	f3 ldir, li;
+	float ldist, dsq;
+	emitter_sample(ks, Eu, e, j, ka, kb, p, ldir, ldist, dsq, li);
+	const float attf = sample_att(ks, ldist, dsq);
+	dark = false;
+	if (dk_on)
+		dark = sample_dark<RTX_SH_SPUNI>(ks, rec, ldir, li, attf, act);
+	const float x = ldist * dot3(ldir, b) * ilr;
+	if (xo)
+		*xo = x;
+	return act && !dark ? order_bucket(x) : RTX_ORD_BUCKETS;
+}
+template <bool COUNT, int WALK>
+__device__ __forceinline__ uint32_t order_begin(const KShadow &ks, const float4 *rec, uint32_t nl, uint32_t base, const uint32_t *cmask,
+						uint32_t *ob, ShadowCount &sc)
+{
+	const float4 q0 = sp_field<true>(rec, 0), q4 = sp_field<true>(rec, 4);
+	if (__float_as_uint(q4.x) & RTX_SP_FAR)
+		return 0u;
+	const f3 p = mk3(q0.x, q0.y, q0.z);
+	const uint32_t obj = __float_as_uint(q4.x);
+	const DEmitter *emitters = unip(ks.emitters);
+	const auto *EM = cptr(emitters);
+	const uint32_t ne = uni(ks.num_emitters);
+	/* the emitter of sample `base` (light_sample's search) and its samples [start, end) */
+	uint32_t e = RTX_NONE, start = 0, end = 0;
+	for (uint32_t k = 0; k < ne && e == RTX_NONE; k++) {
+		const uint32_t eo = EM[k].obj, enl = EM[k].num_lights;
+		if (eo == obj)
+			continue;
+		start = end;
+		end += enl;
+		if (base < end)
+			e = k;
+	}
+	if (e == RTX_NONE || e >= 64u)
+		return 0u;
+	const uint32_t rend = end >= nl ? nl : (end & ~(uint32_t)(WAVE - 1)); /* the packets before it lie inside the emitter */
+	/* a run begins at the emitter's first whole packet and takes all of them, or none: a longer run
+	 * is not cut into ordered pieces */
+	if (rend <= base || base - start >= WAVE || rend - base <= WAVE || rend - base > RTX_ORD_CAP)
+		return 0u;
+	if (WALK == WALK_W8 && ((uni(cmask[e >> 5]) >> (e & 31u)) & 1u)) /* cone-clear: its packets do not walk */
+		return 0u;
+	const uint32_t n = rend - base, npk = (n + WAVE - 1) / WAVE;
+	const bool pclr = (uni(cmask[2 + (e >> 5)]) >> (e & 31u)) & 1u, rclr = (uni(cmask[4 + (e >> 5)]) >> (e & 31u)) & 1u;
+	const DEmitter Eu = emitter_uni(emitters + e);
+	f3 lc;
+	float lr;
+	emitter_sphere(Eu, lc, lr);
+	/* the centre of the bounded objects' world box, as the trees' frame holds it */
+	const f3 b = order_dir(p, lc, mk3(ks.tf.c[0] + ks.tf.cf[0], ks.tf.c[1] + ks.tf.cf[1], ks.tf.c[2] + ks.tf.cf[2]));
+	const float ilr = lr > 0.f ? 1.f / lr : 0.f;
+	const bool dk_on = uni(ks.dark) != 0;
+	uint32_t *ord = ob;
+	uint32_t *rx = ob + RTX_ORD_CAP, *ry = ob + 2 * RTX_ORD_CAP, *rz = ob + 3 * RTX_ORD_CAP;
+	uint32_t cnt = 0; /* lane b: the samples of bucket b */
+	for (uint32_t m = 0; m < npk; m++) {
+		const uint32_t jr = m * WAVE + lane_id(), idx = base + jr;
+		const bool act = idx < rend;
+		bool dark;
+		const uint32_t bk = order_key(ks, rec, Eu, e, idx - start, __float_as_uint(q4.y), __float_as_uint(q4.z), p, b, ilr, dk_on, act, dark);
+		rx[jr] = bk;
+		for (uint32_t k = 0; k < RTX_ORD_BUCKETS; k++) {
+			const uint32_t c = popc64(ballot(bk == k));
+			cnt += lane_id() == k ? c : 0u;
+		}
+		if (COUNT) { /* what light_sample counts for the dark lanes of this packet in index order */
+			const uint32_t na = popc64(ballot(act)), nd = popc64(ballot(act && dark));
+			sc.dark += nd;
+			if (nd == na)
+				sc.dpack += nd;
+			sc.pln += (u64)nd * (pclr ? 0u : uni(ks.num_planes));
+			count_skips(ks, nd, Eu.obj, pclr, rclr, sc);
+		}
+	}
+	uint32_t total;
+	uint32_t first = wave_excl_scan(cnt, &total); /* lane b: the first position of bucket b */
+	for (uint32_t m = 0; m < npk; m++) {
+		const uint32_t jr = m * WAVE + lane_id();
+		const uint32_t bk = rx[jr];
+		uint32_t pos = 0;
+		for (uint32_t k = 0; k < RTX_ORD_BUCKETS; k++) {
+			const u64 mk = ballot(bk == k);
+			if (!mk)
+				continue;
+			const uint32_t f = readlane(first, k);
+			if (bk == k)
+				pos = f + mbcnt(mk);
+			first += lane_id() == k ? popc64(mk) : 0u;
+		}
+		if (bk < RTX_ORD_BUCKETS)
+			ord[pos] = jr;
+		rx[jr] = 0u; /* +0.f: what a dark or idle sample adds */
+		ry[jr] = 0u;
+		rz[jr] = 0u;
+	}
+	lds_sync(); /* the order and the zeroed slots, before other lanes read and write them */
+	if (COUNT) {
+		sc.ordpt += 1;
+		sc.ordray += total;
+	}
+	return 0x80000000u | (npk << 16) | total;
+}
+
 /* ------------------------------------------------------------------------ */
 /* the kernel                                                               */
 /* ------------------------------------------------------------------------ */
@@ -1548,7 +1714,8 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
 /* PATH: 0 both packet layouts (a runtime branch on slot_b: the counting instances), 1 only the
  * wave-uniform packets (slot_b = 64), 2 only the lane slots (slot_b < 64), 3 the lane slots with
  * their cone cull (RTX_OPT_SHADOW_CULL 2), 4 the wave-uniform packets with their dark samples left
- * out of the query (RTX_OPT_SHADOW_DARK).  The product launches a
+ * out of the query (RTX_OPT_SHADOW_DARK), 5 those with the walking points' samples in key order
+ * besides (RTX_OPT_SHADOW_ORDER, order_begin).  The product launches a
  * kernel of one layout, so each gets a register allocation of its own: with both in one kernel a
  * change to the slot loop moved the uniform loop's spills into its walk */
 template <bool COUNT, int OCC, int WALK, int PATH>
@@ -1605,7 +1772,10 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 	 * sample_dark, launched where the option is on and the scene walks a tree.  A scene without a
 	 * tree keeps PATH 1 as it was (with the code present but off, scene3's k_shadow took 52.7
 	 * against 52.4 ms) */
-	constexpr bool DK = PATH == 4 || PATH == 0;
+	constexpr bool DK = PATH == 4 || PATH == 5 || PATH == 0;
+	/* the sample order (RTX_OPT_SHADOW_ORDER) likewise, PATH 5: PATH 4 with order_begin (the dark
+	 * samples follow KShadow.dark at run time, so it serves RTX_OPT_SHADOW_DARK 0 too) */
+	constexpr bool ORD = PATH == 5 || PATH == 0;
 	lds_u32 *stk = (lds_u32 *)&wstk[wv][0][LA ? 0u : lane_id()];
 	ShadowCount sc = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 	u64 rays_total = 0;
@@ -1636,7 +1806,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 		if (lane_id() == 0)
 			off[WAVE] = total;
 		lds_sync();
-		if (PATH == 1 || PATH == 4 || (PATH == 0 && uni(ks.slot_b) == WAVE)) {
+		if (PATH == 1 || PATH == 4 || PATH == 5 || (PATH == 0 && uni(ks.slot_b) == WAVE)) {
 			/* >= 64 lights: every packet is 64 samples of ONE shade point.  The point is wave-uniform
 			 * (its record is read once per packet through one address, no owner search), each lane
 			 * sums its samples over the point's packets, and one butterfly per point reduces them. */
@@ -1660,6 +1830,8 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						wt_w[wv].cm[4] = (w >> 16) & 0xffu;
 						wt_w[wv].cm[5] = 0u;
 						wt_w[wv].cm[6] = ac ? 1u : 0u;
+						if (ORD)
+							wt_w[wv].cm[7] = 0u;
 					}
 					lds_sync();
 				} else {
@@ -1687,13 +1859,15 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						wt_w[wv].cm[4] = (uint32_t)m.lin;
 						wt_w[wv].cm[5] = (uint32_t)(m.lin >> 32);
 						wt_w[wv].cm[6] = ac ? 1u : 0u;
+						if (ORD)
+							wt_w[wv].cm[7] = 0u;
 					}
 					lds_sync();
 				}
 				f3 acc = mk3(0.f, 0.f, 0.f);
 				if (COUNT && uni(wt_w[wv].cm[6]))
 					sc.pclear += nl;
-				for (uint32_t base = 0; base < nl; base += WAVE) {
+				for (uint32_t base = 0; base < nl;) {
 					/* an all-clear point: its packets inside one emitter's samples in clear_run */
 					reread_barrier();
 					if (uni(wt_w[wv].cm[6])) {
@@ -1701,9 +1875,72 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						if (base >= nl)
 							break;
 					}
-					const uint32_t idx = base + lane_id();
-					acc = add3(acc, light_sample<COUNT, WALK, true, LA, false, DK>(ks, rec, 0u, idx, idx < nl, sc, top_q, top_e, stk, t8, wv,
-											    wt_w[wv].cm));
+					uint32_t idx = base + lane_id();
+					bool act = idx < nl;
+					if (ORD) {
+						/* the sample order: cm[7] holds a run's state across its walks (order_begin's word,
+						 * the walked packets in bits 11..15), 0 outside a run.  At a packet outside one,
+						 * an ordered run may begin; inside one, the lanes take the samples of the next 64
+						 * positions of the order */
+						uint32_t st = uni(wt_w[wv].cm[7]);
+						uint32_t *ob = unip(ks.ord);
+						if (ob)
+							ob += (size_t)(blockIdx.x * RTX_SH_NW + wv) * RTX_ORD_WORDS;
+						if (!st && ob && uni(ks.have_tree) && !RTX_DEBUG_NOWALK && !uni(wt_w[wv].cm[6])) {
+							st = order_begin<COUNT, WALK>(ks, rec, nl, base, wt_w[wv].cm, ob, sc);
+							if (st && !(st & 0x7ffu)) {
+								/* every sample dark: nothing to walk, and the slots' +0 leave acc as it is
+								 * (acc is never -0: it starts at +0 and x + y is -0 only for x = y = -0) */
+								base += ((st >> 16) & 31u) * WAVE;
+								continue;
+							}
+							if (st) {
+								if (lane_id() == 0)
+									wt_w[wv].cm[7] = st;
+								lds_sync();
+							}
+						}
+						if (st) {
+							const uint32_t pos = ((st >> 11) & 31u) * WAVE + lane_id();
+							act = pos < (st & 0x7ffu);
+							idx = base + (act ? ob[pos] : 0u);
+						}
+					}
+					const f3 contribution = light_sample<COUNT, WALK, true, LA, false, DK>(ks, rec, 0u, idx, act, sc, top_q, top_e, stk, t8,
+													       wv, wt_w[wv].cm);
+					if (ORD) {
+						/* the run's state again from LDS, and the lane's sample again from the order: neither
+						 * lives in a register across the walk */
+						reread_barrier();
+						const uint32_t st = uni(wt_w[wv].cm[7]);
+						if (st) {
+							uint32_t *ob = unip(ks.ord) + (size_t)(blockIdx.x * RTX_SH_NW + wv) * RTX_ORD_WORDS;
+							const uint32_t pk = (st >> 11) & 31u, npk = (st >> 16) & 31u, no = st & 0x7ffu;
+							const uint32_t pos = pk * WAVE + lane_id();
+							if (pos < no) {
+								const uint32_t jr = ob[pos];
+								ob[RTX_ORD_CAP + jr] = __float_as_uint(contribution.x);
+								ob[2 * RTX_ORD_CAP + jr] = __float_as_uint(contribution.y);
+								ob[3 * RTX_ORD_CAP + jr] = __float_as_uint(contribution.z);
+							}
+							const bool last = (pk + 1) * WAVE >= no;
+							if (last) {
+								lds_sync(); /* every lane's results, before the lanes that add them */
+								for (uint32_t m = 0; m < npk; m++) {
+									const uint32_t jr = m * WAVE + lane_id();
+									acc = add3(acc, mk3(__uint_as_float(ob[RTX_ORD_CAP + jr]), __uint_as_float(ob[2 * RTX_ORD_CAP + jr]),
+											    __uint_as_float(ob[3 * RTX_ORD_CAP + jr])));
+								}
+								base += npk * WAVE;
+							}
+							if (lane_id() == 0)
+								wt_w[wv].cm[7] = last ? 0u : st + (1u << 11);
+							lds_sync();
+							continue;
+						}
+					}
+					acc = add3(acc, contribution);
+					base += WAVE;
 				}
 				const float sx = wave_sum(acc.x), sy = wave_sum(acc.y), sz = wave_sum(acc.z);
 				if (lane_id() == 0) {
@@ -1878,6 +2115,8 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 			atomicAdd(&ctr[RTX_C_SPCLEAR], sc.pclear);
 			atomicAdd(&ctr[RTX_C_SDARK], sc.dark);
 			atomicAdd(&ctr[RTX_C_SDARKPK], sc.dpack);
+			atomicAdd(&ctr[RTX_C_SORDPT], sc.ordpt);
+			atomicAdd(&ctr[RTX_C_SORDRAY], sc.ordray);
 		}
 	}
 }
@@ -2125,6 +2364,104 @@ __global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in,
 	}
 }
 
+/* RTX_KAT_ORDER: order_begin for one shade point and one emitter of nl lights, one wave per record.
+ * The point's record, the emitter, the material, the masks and the wave's slice live in the output
+ * record's tail (rtx_kat.h); k_kat_order_fill writes them first, in a launch of its own, as
+ * order_begin reads them through the scalar cache */
+static_assert(sizeof(DEmitter) <= 256 && sizeof(DMaterial) <= 256, "the KAT record's emitter and material slots");
+__global__ void k_kat_order_fill(uint32_t n, const float *__restrict__ in, float *__restrict__ out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	const float *x = in + (size_t)i * rtx_kat_in_width[RTX_KAT_ORDER];
+	float *y = out + (size_t)i * rtx_kat_out_width[RTX_KAT_ORDER];
+	float4 *rec = (float4 *)(y + RTX_KAT_ORDER_REC);
+	DEmitter *em = (DEmitter *)(y + RTX_KAT_ORDER_REC + 24);
+	DMaterial *mat = (DMaterial *)(y + RTX_KAT_ORDER_REC + 24 + 64);
+	uint32_t *cm = (uint32_t *)y + RTX_KAT_ORDER_REC + 24 + 128;
+	const uint32_t nl = (uint32_t)x[26];
+	DEmitter e;
+	memset(&e, 0, sizeof(e));
+	e.obj = 1u;
+	e.type = x[16] == 0.f ? RTX_SPHERE : RTX_TRIANGLE;
+	e.num_lights = nl;
+	for (int k = 0; k < 3; k++) {
+		e.li[k] = 1.f;
+		e.p0[k] = x[17 + k];
+		e.p1[k] = x[20 + k];
+		e.p2[k] = x[23 + k];
+		e.e1[k] = e.p1[k] - e.p0[k];
+		e.e2[k] = e.p2[k] - e.p0[k];
+	}
+	e.radius = x[29];
+	*em = e;
+	DMaterial m;
+	memset(&m, 0, sizeof(m));
+	for (int k = 0; k < 3; k++)
+		m.ks[k] = x[12 + k];
+	m.shininess = x[15];
+	*mat = m;
+	rec[0] = make_float4(x[0], x[1], x[2], 1.f);
+	rec[1] = make_float4(x[3], x[4], x[5], 1.f);
+	rec[2] = make_float4(x[6], x[7], x[8], 1.f);
+	rec[3] = make_float4(x[9], x[10], x[11], __uint_as_float(0u));
+	rec[4] = make_float4(__uint_as_float(0u), __uint_as_float((uint32_t)x[27]), __uint_as_float((uint32_t)x[28]), __uint_as_float(nl));
+	rec[5] = make_float4(0.f, 0.f, 0.f, 0.f);
+	for (int k = 0; k < 8; k++)
+		cm[k] = 0u;
+}
+__global__ __launch_bounds__(WAVE) void k_kat_order(uint32_t n, const float *__restrict__ in, float *__restrict__ out)
+{
+	const float *x = in + (size_t)blockIdx.x * rtx_kat_in_width[RTX_KAT_ORDER];
+	float *y = out + (size_t)blockIdx.x * rtx_kat_out_width[RTX_KAT_ORDER];
+	uint32_t *yu = (uint32_t *)y;
+	const float4 *rec = (const float4 *)(y + RTX_KAT_ORDER_REC);
+	const DEmitter *em = (const DEmitter *)(y + RTX_KAT_ORDER_REC + 24);
+	const DMaterial *mat = (const DMaterial *)(y + RTX_KAT_ORDER_REC + 24 + 64);
+	uint32_t *cm = yu + RTX_KAT_ORDER_REC + 24 + 128, *ob = cm + 8;
+	const uint32_t nl = (uint32_t)x[26];
+	__shared__ KShadow ks;
+	if (threadIdx.x == 0) {
+		memset(&ks, 0, sizeof(ks));
+		ks.emitters = em;
+		ks.num_emitters = 1u;
+		ks.mats = mat;
+		ks.rng = RTX_RNG_COUNTER;
+		ks.reflection = (int32_t)x[33];
+		ks.attenuation = (int32_t)x[34];
+		ks.att_offset = x[35];
+		ks.dark = x[36] != 0.f ? 1u : 0u;
+		for (int k = 0; k < 3; k++)
+			ks.tf.c[k] = x[30 + k];
+	}
+	__syncthreads();
+	ShadowCount sc = {};
+	const uint32_t st = order_begin<false, WALK_W8>(ks, rec, nl, 0u, cm, ob, sc);
+	if (threadIdx.x == 0) {
+		y[0] = st ? (float)(st & 0x7ffu) : 0.f;
+		y[1] = st ? (float)((st >> 16) & 31u) : 0.f;
+		y[2] = 0.f;
+		y[3] = 0.f;
+	}
+	/* every sample's bucket and x again, from the function order_begin takes them from */
+	const DEmitter Eu = emitter_uni(em);
+	const f3 p = ld3(x);
+	f3 lc;
+	float lr;
+	emitter_sphere(Eu, lc, lr);
+	const f3 b = order_dir(p, lc, mk3(x[30], x[31], x[32]));
+	const float ilr = lr > 0.f ? 1.f / lr : 0.f;
+	for (uint32_t j = threadIdx.x; j < RTX_ORD_CAP; j += WAVE) {
+		bool dark;
+		float xv = 0.f;
+		const uint32_t bk = order_key(ks, rec, Eu, 0u, j, (uint32_t)x[27], (uint32_t)x[28], p, b, ilr, ks.dark != 0, j < nl, dark, &xv);
+		y[4 + j] = st && j < (st & 0x7ffu) ? (float)ob[j] : -1.f;
+		y[4 + RTX_ORD_CAP + j] = (float)bk;
+		y[4 + 2 * RTX_ORD_CAP + j] = j < nl ? xv : 0.f;
+	}
+}
+
 /* the 8-wide BVH's leaf entries: the primitive records they stand for (leafmap[i] = primitive
  * index, RTX_NONE for node entries and holes) */
 __global__ void k_w8_fill(const DPrim *__restrict__ prims, const DMaterial *__restrict__ mats, const uint32_t *__restrict__ leafmap,
@@ -2157,7 +2494,11 @@ extern "C" hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *i
 {
 	if (kind < RTX_KAT_FIRST_SHADOW || kind >= RTX_KAT_NKINDS)
 		return hipErrorInvalidValue;
-	hipLaunchKernelGGL(k_kat_shadow, dim3((n + 255) / 256), dim3(256), 0, stream, kind, n, in, out);
+	if (kind == RTX_KAT_ORDER) {
+		hipLaunchKernelGGL(k_kat_order_fill, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, n, in, out);
+		hipLaunchKernelGGL(k_kat_order, dim3(n), dim3(WAVE), 0, stream, n, in, out);
+	} else
+		hipLaunchKernelGGL(k_kat_shadow, dim3((n + 255) / 256), dim3(256), 0, stream, kind, n, in, out);
 	return hipGetLastError();
 }
 
@@ -2175,41 +2516,46 @@ template <bool C, int O, int W, int P> static hipError_t shadow_slots(uint32_t c
 
 /* the persistent grid: as many workgroups as are resident on the device at once (no more than
  * the work needs); the waves then share the shade points through RTX_C_SPQUEUE */
-template <bool C, int O, int W, int P> static hipError_t launch_shadow_p(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream)
+template <bool C, int O, int W, int P>
+static hipError_t launch_shadow_p(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream, uint32_t max_wgs)
 {
 	uint32_t slots = 0;
 	hipError_t e = shadow_slots<C, O, W, P>(cus, &slots);
 	if (e != hipSuccess)
 		return e;
 	const uint32_t need = (nw + RTX_SH_NW - 1) / RTX_SH_NW;
+	if (ka.ord && max_wgs && slots > max_wgs) /* no more workgroups than the order buffer has slices for */
+		slots = max_wgs;
 	hipLaunchKernelGGL((k_shadow<C, O, W, P>), dim3(need < slots ? need : slots), dim3(WAVE * RTX_SH_NW), 0, stream, ka);
 	return hipGetLastError();
 }
 /* the counting instances keep both layouts in one kernel; the product picks the layout's own */
-template <bool C, int O, int W> static hipError_t launch_shadow(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream)
+template <bool C, int O, int W>
+static hipError_t launch_shadow(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream, uint32_t max_wgs)
 {
 	if constexpr (C) {
-		return launch_shadow_p<C, O, W, 0>(ka, nw, cus, stream);
+		return launch_shadow_p<C, O, W, 0>(ka, nw, cus, stream, max_wgs);
 	} else {
 		if (ka.slot_b == WAVE)
-			return ka.dark ? launch_shadow_p<C, O, W, 4>(ka, nw, cus, stream) : launch_shadow_p<C, O, W, 1>(ka, nw, cus, stream);
+			return ka.ord ? launch_shadow_p<C, O, W, 5>(ka, nw, cus, stream, max_wgs) :
+			       ka.dark ? launch_shadow_p<C, O, W, 4>(ka, nw, cus, stream, max_wgs) : launch_shadow_p<C, O, W, 1>(ka, nw, cus, stream, max_wgs);
 		if (W == WALK_W8 && ka.cull_slots && ka.num_cull)
-			return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 3>(ka, nw, cus, stream);
-		return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 2>(ka, nw, cus, stream);
+			return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 3>(ka, nw, cus, stream, max_wgs);
+		return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 2>(ka, nw, cus, stream, max_wgs);
 	}
 }
 
-template <int W> static hipError_t launch_walk(const KShadow &ka, uint32_t nw, uint32_t cus, int count, hipStream_t stream)
+template <int W> static hipError_t launch_walk(const KShadow &ka, uint32_t nw, uint32_t cus, int count, hipStream_t stream, uint32_t max_wgs)
 {
 	if (count)
-		return launch_shadow<true, 1, W>(ka, nw, cus, stream);
+		return launch_shadow<true, 1, W>(ka, nw, cus, stream, max_wgs);
 #if RTX_MEASURE
 	/* occupancy variant (measurement builds): RTX_SHADOW_OCC = 1 (the compiler's choice) */
 	const char *env = getenv("RTX_SHADOW_OCC");
 	if (env && atoi(env) != RTX_SHADOW_OCC_DEFAULT)
-		return launch_shadow<false, 1, W>(ka, nw, cus, stream);
+		return launch_shadow<false, 1, W>(ka, nw, cus, stream, max_wgs);
 #endif
-	return launch_shadow<false, RTX_SHADOW_OCC_DEFAULT, W>(ka, nw, cus, stream);
+	return launch_shadow<false, RTX_SHADOW_OCC_DEFAULT, W>(ka, nw, cus, stream, max_wgs);
 }
 
 /* the walk k_shadow runs for a scene: the 8-wide BVH when built, else the threaded BVH2 */
@@ -2224,6 +2570,11 @@ extern "C" hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes)
 		uint32_t a4 = 0;
 		e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 4>(cus, &a4);
 		a = a > a4 ? a : a4;
+	}
+	if (e == hipSuccess) {
+		uint32_t a5 = 0;
+		e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 5>(cus, &a5);
+		a = a > a5 ? a : a5;
 	}
 	if (e == hipSuccess)
 		e = shadow_slots<false, RTX_SHADOW_OCC_SLOT, WALK_W8, 2>(cus, &a2);
@@ -2268,7 +2619,6 @@ static hipError_t shadow_scene_args(const DScene *S, uint32_t cus, KShadow &ka)
 		if (!S->w8spill || S->w8spill_lanes < lanes)
 			return hipErrorInvalidValue;
 	}
-	ka.prims = S->prims;
 	ka.recs = (const char *)S->nodes;
 	ka.qnodes = S->qnodes;
 	ka.top = S->top;
@@ -2346,6 +2696,15 @@ extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const
 	/* the points' masks ahead of the kernel (k_point_masks, pmask: a word per record of the chunk): where
 	 * k_shadow would form them, one point per wave (the wave-uniform packets), and a byte per mask holds
 	 * the emitters; else k_shadow forms them itself */
+	/* the sample order: where shadow rays walk a tree, with the waves' slices for this launch's grid */
+	ka.ord = nullptr;
+	uint32_t ord_wgs = 0; /* the workgroups its buffer has slices for: the grid is held to them */
+	if (S->order && slot_b == WAVE && ka.have_tree) {
+		if (!S->ordbuf || S->ordbuf_waves < RTX_SH_NW)
+			return hipErrorInvalidValue;
+		ka.ord = S->ordbuf;
+		ord_wgs = S->ordbuf_waves / RTX_SH_NW;
+	}
 	ka.pm = nullptr;
 	if (pmask && slot_b == WAVE && ka.num_emitters <= 8u && (ka.num_cull || ka.point)) {
 		hipLaunchKernelGGL(k_point_masks, dim3((n_sp + RTX_PM_BLOCK - 1) / RTX_PM_BLOCK), dim3(RTX_PM_BLOCK), 0, stream, ka, pmask);
@@ -2357,8 +2716,8 @@ extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const
 			*premasked = 1;
 	}
 	if (walk_of(S) == WALK_W8)
-		return launch_walk<WALK_W8>(ka, nw, cus, count, stream);
-	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream);
+		return launch_walk<WALK_W8>(ka, nw, cus, count, stream, ord_wgs);
+	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream, ord_wgs);
 }
 
 /* n caller's shadow rays through shadow_query (k_shadow_rays): the instance follows the scene as

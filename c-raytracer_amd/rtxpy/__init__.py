@@ -203,8 +203,9 @@ def write_stl(path, tris):
     _check_scene(scene_lib().rtx_stl_write(os.fsencode(path), tris.shape[0], tris.ctypes.data))
 
 
-def _with_point_stats(s, p, d=None, m=None):
-    """the rtx_point_stats (and rtx_dark_stats, rtx_premask_stats) counters as attributes of the Stats beside them"""
+def _with_point_stats(s, p, d=None, m=None, o=None):
+    """the rtx_point_stats (and rtx_dark_stats, rtx_premask_stats, rtx_order_stats) counters as attributes of the Stats
+    beside them"""
     for f, _ in abi.PointStats._fields_:
         setattr(s, f, getattr(p, f))
     if d is not None:
@@ -213,6 +214,9 @@ def _with_point_stats(s, p, d=None, m=None):
     if m is not None:
         for f, _ in abi.PremaskStats._fields_:
             setattr(s, f, getattr(m, f))
+    if o is not None:
+        for f, _ in abi.OrderStats._fields_:
+            setattr(s, f, getattr(o, f))
     return s
 
 
@@ -300,7 +304,9 @@ class Renderer:
         _check(self.lib.rtx_get_dark_stats(self._ctx, C.byref(d)))
         m = abi.PremaskStats()
         _check(self.lib.rtx_get_premask_stats(self._ctx, C.byref(m)))
-        return _with_point_stats(s, p, d, m)
+        o = abi.OrderStats()
+        _check(self.lib.rtx_get_order_stats(self._ctx, C.byref(o)))
+        return _with_point_stats(s, p, d, m, o)
 
     def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
         """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
@@ -495,7 +501,9 @@ class Group:
         _check(self.lib.rtx_group_get_dark_stats(self._g, C.byref(d)))
         m = abi.PremaskStats()
         _check(self.lib.rtx_group_get_premask_stats(self._g, C.byref(m)))
-        return _with_point_stats(s, p, d, m)
+        o = abi.OrderStats()
+        _check(self.lib.rtx_group_get_order_stats(self._g, C.byref(o)))
+        return _with_point_stats(s, p, d, m, o)
 
     def device_stats(self, r):
         s = Stats()
@@ -506,7 +514,9 @@ class Group:
         _check(self.lib.rtx_group_device_dark_stats(self._g, r, C.byref(d)))
         m = abi.PremaskStats()
         _check(self.lib.rtx_group_device_premask_stats(self._g, r, C.byref(m)))
-        return _with_point_stats(s, p, d, m)
+        o = abi.OrderStats()
+        _check(self.lib.rtx_group_device_order_stats(self._g, r, C.byref(o)))
+        return _with_point_stats(s, p, d, m, o)
 
     def member(self, r):
         """what the runtime reports about member r (rtx_group_member_info): its device, its RCCL

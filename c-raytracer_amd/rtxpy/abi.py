@@ -89,6 +89,11 @@ class DarkStats(C.Structure):
     _fields_ = [("shadow_dark_rays", C.c_uint64), ("shadow_dark_packet_rays", C.c_uint64)]
 
 
+class OrderStats(C.Structure):
+    """rtx_order_stats: the counters of RTX_OPT_SHADOW_ORDER (rtxpy's stats() set them on the Stats they return)"""
+    _fields_ = [("shadow_ordered_points", C.c_uint64), ("shadow_ordered_rays", C.c_uint64)]
+
+
 class PremaskStats(C.Structure):
     """rtx_premask_stats: whether RTX_OPT_SHADOW_PREMASK took effect (rtxpy's stats() set it on the Stats they return)"""
     _fields_ = [("premask_points", C.c_uint64)]
@@ -111,7 +116,8 @@ RTX_FRAME_AUTO, RTX_FRAME_WORLD = 0, 1
 RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_OPT_SHADOW_GRAB, \
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
     RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES, \
-    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16
+    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK, RTX_OPT_SHADOW_ORDER = \
+    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 
@@ -195,19 +201,20 @@ DENOISE_DEFAULTS = {"iterations": 1, "sigma_color": 0.004, "sigma_normal": 0.05,
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
     KAT_MORTON, KAT_U32, KAT_GI_DIR, KAT_REFRACT, KAT_ANY_TRI, KAT_SPH_LIGHT_SH, KAT_BOX_Q, KAT_SPEC_POW, \
-    KAT_BOX_Q8, KAT_PLANE_CLEAR, KAT_LIN_CLEAR, KAT_DARK = range(20)
-KAT_IN = [16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26]
-KAT_OUT = [2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7]
+    KAT_BOX_Q8, KAT_PLANE_CLEAR, KAT_LIN_CLEAR, KAT_DARK, KAT_ORDER = range(21)
+KAT_IN = [16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37]
+KAT_OUT = [2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332]
 KAT_NAMES = ["moller", "sphere", "plane", "slab", "noise", "texture", "sph_light", "tri_light", "morton", "u32",
-             "gi_dir", "refract", "any_tri", "sph_light_sh", "box_q", "spec_pow", "box_q8", "plane_clear", "lin_clear", "dark"]
+             "gi_dir", "refract", "any_tri", "sph_light_sh", "box_q", "spec_pow", "box_q8", "plane_clear", "lin_clear", "dark", "order"]
 
 # symbols include/rtx.h declares (checked by tests/test_abi.py)
 RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload_scene", "rtx_render",
-               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_premask_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
+               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_order_stats", "rtx_get_premask_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
                "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree", "rtx_read_bvh2",
                "rtx_group_set_builder", "rtx_group_set_option", "rtx_group_upload_scene", "rtx_group_render", "rtx_group_get_stats", "rtx_group_device_stats",
                "rtx_group_get_point_stats", "rtx_group_device_point_stats",
                "rtx_group_get_dark_stats", "rtx_group_device_dark_stats",
+               "rtx_group_get_order_stats", "rtx_group_device_order_stats",
                "rtx_group_get_premask_stats", "rtx_group_device_premask_stats",
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
@@ -274,6 +281,8 @@ def declare_rtx(lib):
     lib.rtx_get_point_stats.restype = C.c_int
     lib.rtx_get_dark_stats.argtypes = [C.c_void_p, C.POINTER(DarkStats)]
     lib.rtx_get_dark_stats.restype = C.c_int
+    lib.rtx_get_order_stats.argtypes = [C.c_void_p, C.POINTER(OrderStats)]
+    lib.rtx_get_order_stats.restype = C.c_int
     lib.rtx_get_premask_stats.argtypes = [C.c_void_p, C.POINTER(PremaskStats)]
     lib.rtx_get_premask_stats.restype = C.c_int
     lib.rtx_close.argtypes = [C.c_void_p]
@@ -324,6 +333,10 @@ def declare_rtx(lib):
     lib.rtx_group_get_dark_stats.restype = C.c_int
     lib.rtx_group_device_dark_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(DarkStats)]
     lib.rtx_group_device_dark_stats.restype = C.c_int
+    lib.rtx_group_get_order_stats.argtypes = [C.c_void_p, C.POINTER(OrderStats)]
+    lib.rtx_group_get_order_stats.restype = C.c_int
+    lib.rtx_group_device_order_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(OrderStats)]
+    lib.rtx_group_device_order_stats.restype = C.c_int
     lib.rtx_group_get_premask_stats.argtypes = [C.c_void_p, C.POINTER(PremaskStats)]
     lib.rtx_group_get_premask_stats.restype = C.c_int
     lib.rtx_group_device_premask_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(PremaskStats)]

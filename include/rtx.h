@@ -180,7 +180,10 @@ void rtx_params_default(rtx_params *p);
 typedef struct rtx_stats {
 	uint64_t closest_rays;       /* cast_ray() calls (render.c:136) */
 	uint64_t shadow_rays;        /* is_light_blocked() calls (render.c:126) */
-	/* only with count_traversal: per-ray work summed over all rays (closest + shadow) */
+	/* only with count_traversal: per-ray work summed over all rays (closest + shadow).  A shadow ray's
+	 * tests of transparent leaves of the 8-wide tree count where its walk meets them, whether or not an
+	 * opaque hit ends the ray before the wave runs them (they are deferred): the counts do not depend on
+	 * which rays share a packet */
 	uint64_t node_visits;        /* BVH inner nodes fetched (2 child boxes tested) */
 	uint64_t tri_tests;
 	uint64_t sphere_tests;
@@ -259,6 +262,14 @@ typedef struct rtx_dark_stats {
 	                                   * and no walk for the packet */
 } rtx_dark_stats;
 
+/* What RTX_OPT_SHADOW_ORDER put in order, only with count_traversal; a struct of its own for the same
+ * reason (rtx_get_order_stats, after the render) */
+typedef struct rtx_order_stats {
+	uint64_t shadow_ordered_points; /* runs of one emitter's light samples of a shade point walked in key order
+	                                 * (a point counts once per emitter it orders) */
+	uint64_t shadow_ordered_rays;   /* the shadow rays walked in them (their dark samples are not walked) */
+} rtx_order_stats;
+
 /* Whether RTX_OPT_SHADOW_PREMASK took effect, with or without count_traversal; a struct of its own for
  * the same reason (rtx_get_premask_stats, after the render) */
 typedef struct rtx_premask_stats {
@@ -293,6 +304,7 @@ int rtx_render_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *pa
 int rtx_get_stats(const rtx_ctx *ctx, rtx_stats *out);
 int rtx_get_point_stats(const rtx_ctx *ctx, rtx_point_stats *out);
 int rtx_get_dark_stats(const rtx_ctx *ctx, rtx_dark_stats *out);
+int rtx_get_order_stats(const rtx_ctx *ctx, rtx_order_stats *out);
 int rtx_get_premask_stats(const rtx_ctx *ctx, rtx_premask_stats *out);
 /* Builder used by subsequent rtx_upload_scene calls on this context (RTX_BUILD_*). */
 int rtx_set_builder(rtx_ctx *ctx, int builder);
@@ -352,11 +364,16 @@ enum rtx_option {
 	                               * the cone cull has not cleared the packet, in scenes whose transmittances are
 	                               * finite with |kt| <= 1 and whose emitters are finite; 0: every sample is
 	                               * queried.  RTX_OPT_SHADOW_CULL 0 turns this off too */
-	RTX_OPT_SHADOW_PREMASK = 16   /* 1 (default): the masks of RTX_OPT_SHADOW_CULL and RTX_OPT_SHADOW_POINT are formed
+	RTX_OPT_SHADOW_PREMASK = 16,  /* 1 (default): the masks of RTX_OPT_SHADOW_CULL and RTX_OPT_SHADOW_POINT are formed
 	                               * by a kernel of their own ahead of k_shadow, one shade point per lane, where
 	                               * k_shadow would form them one point per wave (points with 64 light samples
 	                               * or more) and the scene has at most 8 emitters (same masks, same image);
 	                               * 0: k_shadow forms them itself */
+	RTX_OPT_SHADOW_ORDER = 17     /* 1 (default): a shade point that walks the tree takes the light samples of one
+	                               * emitter, more than 64 and at most 1024 of them, in the order of where their
+	                               * light points lie across the cone toward the emitter (16 buckets), so the 64
+	                               * rays of a packet cross much the same part of the tree; the samples' terms
+	                               * are still added in index order (same image, bit for bit); 0: index order */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -523,6 +540,9 @@ int rtx_group_device_point_stats(const rtx_group *g, int r, rtx_point_stats *out
 /* rtx_dark_stats likewise */
 int rtx_group_get_dark_stats(const rtx_group *g, rtx_dark_stats *out);
 int rtx_group_device_dark_stats(const rtx_group *g, int r, rtx_dark_stats *out);
+/* rtx_order_stats likewise */
+int rtx_group_get_order_stats(const rtx_group *g, rtx_order_stats *out);
+int rtx_group_device_order_stats(const rtx_group *g, int r, rtx_order_stats *out);
 /* rtx_premask_stats likewise */
 int rtx_group_get_premask_stats(const rtx_group *g, rtx_premask_stats *out);
 int rtx_group_device_premask_stats(const rtx_group *g, int r, rtx_premask_stats *out);

@@ -44,6 +44,15 @@
  *                     direction ldir and length ldist, 0 when li is not finite or |kt| > 1 as the scene's flag
  *                     has it; terms: shade_terms of the sample for li; terms_kt: for li * kt, the product a
  *                     walk through one transparent surface leaves)
+ * -- k_shadow's sample order (rtx_shadow.hip order_begin), one wave per record --
+ * KAT_ORDER  (20)    P3 n3 view3 kd3 ks3 shin etype v0_3 v1_3 v2_3 nl key_lo key_hi r centre3 refl att att_offset dark = 37
+ *                    n_ord packets - - order[1024] bucket[1024] x[1024] scratch = 7332
+ *                    (the shade point P of normal n, view direction and material (kd, ks, shin) on object 0; one
+ *                     emitter, object 1, of nl lights: etype 0 the sphere (v0, r), 1 the triangle v0 v1 v2; the
+ *                     point's draw key (integers below 2^24); centre: of the bounded objects' box; dark: the
+ *                     RTX_OPT_SHADOW_DARK flag.  n_ord: the samples in the order (0: the run is not ordered),
+ *                     order[pos]: the sample at position pos (-1 beyond n_ord), bucket[j]: sample j's bucket
+ *                     (16: dark, or j >= nl), x[j]: its key value; scratch: the kernel's own records)
  * Texture records use the params' u32conv for the float->uint32 conversion.
  */
 #ifndef RTX_KAT_H
@@ -70,11 +79,16 @@ enum rtx_kat_kind {
 	RTX_KAT_PLANE_CLEAR = 17,
 	RTX_KAT_LIN_CLEAR = 18,
 	RTX_KAT_DARK = 19,
-	RTX_KAT_NKINDS = 20,
+	RTX_KAT_ORDER = 20,
+	RTX_KAT_NKINDS = 21,
 };
 #define RTX_KAT_FIRST_SHADOW RTX_KAT_ANY_TRI /* kinds >= this run in rtx_shadow.hip */
 
-static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26 };
-static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7 };
+static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37 };
+static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332 };
+/* KAT_ORDER's output record: 4 header words, order / bucket / x (1024 each), then the kernel's scratch from word
+ * RTX_KAT_ORDER_REC on: the shade-point record (24 words), the emitter (64), the material (64), the masks (8) and
+ * the wave's slice (4096) */
+#define RTX_KAT_ORDER_REC (4 + 3 * 1024)
 
 #endif

@@ -594,7 +594,50 @@ int main(int argc, char **argv)
 	double wk_steps = 0, wk_sorted = 0, wk_part = 0, wk_lanes = 0, wk_walkers = 0;
 	std::vector<double> cone_leaf_hist(8, 0.0), cone_depth_hist(16, 0.0), ws_depth(16, 0.0);
 	const int order = getenv("W8SIM_ORDER") ? atoi(getenv("W8SIM_ORDER")) : 0;
-	const bool sort_samples = getenv("W8SIM_SORT") && atoi(getenv("W8SIM_SORT"));
+	/* W8SIM_SORT: the order a point's samples are packed in.  0 index order, 1 buckets of the first
+	 * draw, 2.. keys of the light point's position across the cone (see the per-point code) */
+	const int sort_mode = getenv("W8SIM_SORT") ? atoi(getenv("W8SIM_SORT")) : 0;
+	/* the emitter's bounding sphere (k_shadow's emitter_sphere) */
+	auto emitter_ball = [&](double Lc[3], double &lr) {
+		if (E.type == RTX_SPHERE) {
+			for (int a = 0; a < 3; a++)
+				Lc[a] = E.p0[a];
+			lr = E.radius;
+		} else {
+			for (int a = 0; a < 3; a++)
+				Lc[a] = E.p0[a] + (E.e1[a] + E.e2[a]) / 3.0;
+			lr = 0;
+			for (int k = 0; k < 3; k++) {
+				double q = 0;
+				for (int a = 0; a < 3; a++) {
+					const double v = E.p0[a] + (k == 1 ? E.e1[a] : k == 2 ? E.e2[a] : 0.0) - Lc[a];
+					q += v * v;
+				}
+				lr = std::max(lr, sqrt(q));
+			}
+		}
+		lr = lr * (1 + 1e-5) + 1e-6;
+	};
+	/* the light point of the draws (u1, u2) as seen from the shade point P */
+	auto sample_point = [&](const float P[3], float u1, float u2, float Lp[3]) {
+		if (E.type == RTX_SPHERE) {
+			const float inc = u1 * 2.f * 3.1415927f, az = u2 * 2.f * 3.1415927f;
+			float ld[3] = { E.radius * cosf(az) * sinf(inc), E.radius * sinf(az) * sinf(inc), E.radius * cosf(inc) };
+			const float nr[3] = { E.p0[0] - P[0], E.p0[1] - P[1], E.p0[2] - P[2] };
+			if (nr[0] * ld[0] + nr[1] * ld[1] + nr[2] * ld[2] != 0.f)
+				for (int a = 0; a < 3; a++)
+					ld[a] = -ld[a];
+			for (int a = 0; a < 3; a++)
+				Lp[a] = E.p0[a] + ld[a];
+		} else {
+			if (u1 + u2 > 1) {
+				u1 = 1 - u1;
+				u2 = 1 - u2;
+			}
+			for (int a = 0; a < 3; a++)
+				Lp[a] = E.p0[a] + u1 * E.e1[a] + u2 * E.e2[a];
+		}
+	};
 	const bool strat = getenv("W8SIM_STRAT") && atoi(getenv("W8SIM_STRAT")); /* RTX_RNG_STRAT light samples */
 	/* dark samples (RTX_OPT_SHADOW_DARK): rays, packets, and the wave steps / leaf rounds of the packets
 	 * with and without their dark lanes, over the points the cone does not clear (W8SIM_CONE=1) */
@@ -720,14 +763,92 @@ int main(int argc, char **argv)
 		std::vector<uint32_t> sord(nl);
 		for (uint32_t j = 0; j < nl; j++)
 			sord[j] = j;
-		if (sort_samples && nl > 64) {
+		uint32_t npk = nl; /* the samples the packets hold */
+		if (sort_mode == 1 && nl > 64) {
 			const uint32_t G = (nl + 63) / 64;
 			std::stable_sort(sord.begin(), sord.end(), [&](uint32_t a, uint32_t b) {
 				return (uint32_t)(su1[a] * G) < (uint32_t)(su1[b] * G);
 			});
 		}
+		if (sort_mode >= 2 && nl > 64) {
+			/* keys of the light point's position across the cone from the shade point to the
+			 * emitter's bounding sphere (c, lr): x along b1 = a unit vector across the axis (the
+			 * axis crossed with the world axis it is least along), y along b2 = axis x b1; or, from
+			 * mode 9 on, x along the part of (tree centre - p) across the axis.  The dark samples
+			 * are taken out of the order (they are never walked) and the rest packed densely */
+			double Lc[3], lr, ax[3], b1[3], b2[3], L = 0;
+			emitter_ball(Lc, lr);
+			for (int a = 0; a < 3; a++) {
+				ax[a] = Lc[a] - P[a];
+				L += ax[a] * ax[a];
+			}
+			L = sqrt(std::max(L, 1e-60));
+			for (int a = 0; a < 3; a++)
+				ax[a] /= L;
+			double ref[3] = { 0, 0, 0 };
+			if (sort_mode >= 9) {
+				for (int a = 0; a < 3; a++)
+					ref[a] = 0.5 * (blo[a] + bhi[a]) - P[a];
+			} else {
+				int k = 0;
+				for (int a = 1; a < 3; a++)
+					if (fabs(ax[a]) < fabs(ax[k]))
+						k = a;
+				ref[k] = 1;
+			}
+			const double ra = ref[0] * ax[0] + ref[1] * ax[1] + ref[2] * ax[2];
+			double bn = 0;
+			for (int a = 0; a < 3; a++) {
+				b1[a] = ref[a] - ra * ax[a];
+				bn += b1[a] * b1[a];
+			}
+			bn = sqrt(std::max(bn, 1e-60));
+			for (int a = 0; a < 3; a++)
+				b1[a] /= bn;
+			b2[0] = ax[1] * b1[2] - ax[2] * b1[1];
+			b2[1] = ax[2] * b1[0] - ax[0] * b1[2];
+			b2[2] = ax[0] * b1[1] - ax[1] * b1[0];
+			std::vector<double> key(nl);
+			std::vector<char> dark(nl, 0);
+			for (uint32_t j = 0; j < nl; j++) {
+				float Lp[3];
+				sample_point(P, su1[j], su2[j], Lp);
+				double d[3] = { Lp[0] - P[0], Lp[1] - P[1], Lp[2] - P[2] }, x = 0, y = 0;
+				const double dist = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+				for (int a = 0; a < 3; a++) {
+					x += (Lp[a] - Lc[a]) * b1[a] / lr;
+					y += (Lp[a] - Lc[a]) * b2[a] / lr;
+					d[a] /= dist;
+				}
+				if ((uint32_t)psh[pi][6] != RTX_NONE)
+					dark[j] = sample_is_dark(&psh[pi][0], &psh[pi][3], sc->materials[sc->objects[(uint32_t)psh[pi][6]].material], d);
+				auto bucket = [](double v, int n) { return (double)std::min(n - 1, std::max(0, (int)floor((v + 1) * 0.5 * n))); };
+				switch (sort_mode) {
+				case 2: case 9: key[j] = bucket(x, 16); break;  /* 16 buckets of x */
+				case 3: case 10: key[j] = x; break;             /* x, full sort */
+				case 4: key[j] = bucket(y, 16); break;          /* 16 buckets of y */
+				case 5: case 11: key[j] = y; break;             /* y, full sort */
+				case 6: key[j] = atan2(y, x); break;            /* the angle about the axis, full sort */
+				case 7: {                                       /* 8 x 8 Morton cells */
+					const uint32_t cx = (uint32_t)bucket(x, 8), cy = (uint32_t)bucket(y, 8);
+					uint32_t m = 0;
+					for (int b = 0; b < 3; b++)
+						m |= ((cx >> b) & 1u) << (2 * b) | ((cy >> b) & 1u) << (2 * b + 1);
+					key[j] = m;
+					break;
+				}
+				default: key[j] = bucket(x, 8); break;          /* 8: 8 buckets of x */
+				}
+			}
+			std::stable_sort(sord.begin(), sord.end(), [&](uint32_t a, uint32_t b) {
+				return dark[a] != dark[b] ? dark[a] < dark[b] : key[a] < key[b];
+			});
+			npk = 0;
+			for (uint32_t j = 0; j < nl; j++)
+				npk += !dark[j];
+		}
 		std::vector<uint32_t> pt_len; /* every sample's walk length (visits) of this point */
-		for (uint32_t b0 = 0; b0 < nl; b0 += 64) {
+		for (uint32_t b0 = 0; b0 < npk; b0 += 64) {
 			std::vector<uint32_t> visits_lane, leaf_at; /* per-lane per-visit leaf hits */
 			std::vector<std::vector<uint32_t>> leaves(64), seq(64);
 			uint32_t block_at[64]; /* ordinal (in discovery order) of the lane's blocking leaf test, or ~0 */
@@ -736,27 +857,10 @@ int main(int argc, char **argv)
 			float lane_d[64][3], lane_dist[64];
 			uint32_t maxv = 0, imm_len[64] = {};
 			bool lane_dark[64] = {};
-			for (uint32_t l = 0; l < 64 && b0 + l < nl; l++) {
+			for (uint32_t l = 0; l < 64 && b0 + l < npk; l++) {
 				const uint32_t j = b0 + l;
-				float u1 = su1[sord[j]], u2 = su2[sord[j]];
 				float Lp[3];
-				if (E.type == RTX_SPHERE) {
-					const float inc = u1 * 2.f * 3.1415927f, az = u2 * 2.f * 3.1415927f;
-					float ld[3] = { E.radius * cosf(az) * sinf(inc), E.radius * sinf(az) * sinf(inc), E.radius * cosf(inc) };
-					const float nr[3] = { E.p0[0] - P[0], E.p0[1] - P[1], E.p0[2] - P[2] };
-					if (nr[0] * ld[0] + nr[1] * ld[1] + nr[2] * ld[2] != 0.f)
-						for (int a = 0; a < 3; a++)
-							ld[a] = -ld[a];
-					for (int a = 0; a < 3; a++)
-						Lp[a] = E.p0[a] + ld[a];
-				} else {
-					if (u1 + u2 > 1) {
-						u1 = 1 - u1;
-						u2 = 1 - u2;
-					}
-					for (int a = 0; a < 3; a++)
-						Lp[a] = E.p0[a] + u1 * E.e1[a] + u2 * E.e2[a];
-				}
+				sample_point(P, su1[sord[j]], su2[sord[j]], Lp);
 				double d[3] = { Lp[0] - P[0], Lp[1] - P[1], Lp[2] - P[2] };
 				const double dist = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
 				for (int a = 0; a < 3; a++)
@@ -907,11 +1011,11 @@ int main(int argc, char **argv)
 				maxv = std::max(maxv, nv_imm);
 				imm_len[l] = nv_imm;
 			}
-			for (uint32_t l = 0; l < 64 && b0 + l < nl; l++)
+			for (uint32_t l = 0; l < 64 && b0 + l < npk; l++)
 				allseq.emplace_back(seq[l].begin(), seq[l].begin() + std::min<size_t>(seq[l].size(), imm_len[l]));
 			S.packets++;
 			if (!cone_sim || !cone_empty) {
-				const uint32_t nlanes = std::min<uint32_t>(64, nl - b0);
+				const uint32_t nlanes = std::min<uint32_t>(64, npk - b0);
 				uint32_t nd = 0, mv[2] = { 0, 0 };
 				for (uint32_t l = 0; l < nlanes; l++) {
 					nd += lane_dark[l];
@@ -935,7 +1039,7 @@ int main(int argc, char **argv)
 				}
 			}
 			if (occ_sim) {
-				const uint32_t nlanes = std::min<uint32_t>(64, nl - b0);
+				const uint32_t nlanes = std::min<uint32_t>(64, npk - b0);
 				for (uint32_t l = 0; l < nlanes; l++)
 					S.blocked_samples += blk_obj[l] != RTX_NONE;
 				for (int v = 0; v < 4; v++) {
@@ -1000,7 +1104,7 @@ int main(int argc, char **argv)
 				}
 			}
 			S.wave_steps += maxv;
-			for (uint32_t l = 0; l < 64 && b0 + l < nl; l++)
+			for (uint32_t l = 0; l < 64 && b0 + l < npk; l++)
 				pt_len.push_back(imm_len[l]);
 			for (uint32_t i = 0; i < maxv; i++) {
 				std::vector<uint32_t> at(64, ~0u);
@@ -1020,7 +1124,7 @@ int main(int argc, char **argv)
 					const DW8 &N = w8[first];
 					const double org[3] = { (double)(N.w[0] & 0xFFFF), (double)(N.w[0] >> 16), (double)(N.w[1] & 0xFFFF) };
 					const int ex[3] = { (int)((N.w[1] >> 16) & 15), (int)((N.w[1] >> 20) & 15), (int)((N.w[1] >> 24) & 15) };
-					const uint32_t nl2 = std::min<uint32_t>(64, nl - b0);
+					const uint32_t nl2 = std::min<uint32_t>(64, npk - b0);
 					S.u_steps++;
 					S.u_kids += __builtin_popcount(N.w[3] & 0xFFu);
 					double imn[2][3], imx[2][3], tlx[2] = { 0, 0 };
@@ -1201,6 +1305,9 @@ int main(int argc, char **argv)
 	       "packets take %.4f of the wave steps and %.4f of the leaf rounds\n",
 	       cone_sim ? "points the cone does not clear" : "all points", dk_rays / std::max(1.0, dk_all), dk_pk / std::max(1.0, dk_pk_all),
 	       dk_steps[1] / std::max(1.0, dk_steps[0]), dk_rounds[1] / std::max(1.0, dk_rounds[0]));
+	if (cone_sim)
+		printf("sample order W8SIM_SORT=%d, points the cone does not clear, dark lanes out: wave steps %.0f  leaf rounds %.0f  "
+		       "packets %.0f\n", sort_mode, dk_steps[1], dk_rounds[1], dk_pk_all);
 	printf("lane refill (a finished lane takes the point's next light sample when >= T lanes are idle), per point:\n"
 	       "   T   wave steps (uniform)   refill rounds   cost (178/divergent + 95/uniform step + 220/refill)\n");
 	for (int k = 0; k < 6; k++)
