@@ -1,8 +1,8 @@
 /*
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
- * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser)
- * and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
+ * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
+ * rtx_passes.cpp (multi-pass rendering) and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
@@ -208,6 +208,12 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float> d_dn_rgb;
 	DevBuf<unsigned long long> d_dn_ctr; /* k_dn_pack's hit-pixel count */
 	rtx_denoise_stats dn_stats{};
+	/* multi-pass rendering (rtx_render_passes*): grow-only scratch of its own */
+	DevBuf<float> d_pass_rgb;     /* the pass being rendered */
+	DevBuf<double> d_pass_state;  /* mean r, g, b and m2 r, g, b, one double per pixel each (rtx_passes.hip) */
+	DevBuf<double> d_pass_sums;   /* the blocks' partial sums of the error, then their two totals */
+	DevBuf<float> d_pass_var;     /* the host-buffer call's device copy of the variance */
+	rtx_pass_stats pass_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;

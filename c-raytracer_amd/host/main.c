@@ -18,6 +18,12 @@
  *   --u32 wrap   float->uint32 texture conversion of a generic x86-64 build
  *                (default: AVX-512 saturating, like -march=native on AVX-512 hosts)
  *   --denoise    the rendered rgb through rtx_frame_features + rtx_denoise (defaults) before it is saved
+ *   --passes K   the frame rendered K times (seed + k) and the passes' mean saved (rtx_render_passes)
+ *   --aa         pass k at its own sub-pixel offset (RTX_PASS_JITTER); 16 passes unless --passes is given
+ *   --lens APERTURE FOCUS_DISTANCE   a thin lens of that radius focused at that distance (world units),
+ *                pass k from its own lens point; 16 passes unless --passes is given
+ *   --target-error E   stop after the first pass (of at least 2) whose error estimate is <= E
+ *                The multi-pass flags render on one device; --denoise then filters the mean.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,7 +54,11 @@ static const char *HELPTEXT =
 	"[-g] (string)                    : DEFAULT = ambient : global illumination model (ambient | path).\n"
 	"[-f]                             : DEFAULT = OFF     : save raw output for post-processing.\n"
 	"[--gpus N] [--device D] [--seed S] [--rng counter|strat|const] [--u32 sat|wrap]\n"
-	"[--denoise]                      : DEFAULT = OFF     : filter the image with the edge-aware denoiser before saving.\n";
+	"[--denoise]                      : DEFAULT = OFF     : filter the image with the edge-aware denoiser before saving.\n"
+	"[--passes] (integer)             : DEFAULT = 1       : render the frame this many times (seed + k) and save the mean.\n"
+	"[--aa]                           : DEFAULT = OFF     : anti-aliasing: every pass at its own sub-pixel offset (16 passes unless --passes).\n"
+	"[--lens] (float) (float)         : DEFAULT = OFF     : thin lens: aperture radius and focus distance (16 passes unless --passes).\n"
+	"[--target-error] (float)         : DEFAULT = 0       : stop once the passes' error estimate is at most this (one GPU only).\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -107,6 +117,36 @@ int main(int argc, char **argv)
 		p.u32conv = RTX_U32_WRAP;
 	if (ngpu < 1)
 		ngpu = 1;
+	/* multi-pass rendering (rtx_render_passes): any of its flags turns it on, on one context */
+	rtx_pass_params pp;
+	rtx_pass_params_default(&pp);
+	int multipass = 0, lens = 0;
+	double focus_distance = 0.0;
+	if ((idx = argv_find(argc, argv, "--passes", 1))) {
+		pp.passes = (uint32_t)strtoul(argv[idx + 1], NULL, 10);
+		multipass = 1;
+	}
+	if (argv_find(argc, argv, "--aa", 0)) {
+		pp.flags |= RTX_PASS_JITTER;
+		if (!multipass)
+			pp.passes = 16;
+		multipass = 1;
+	}
+	if ((idx = argv_find(argc, argv, "--lens", 2))) {
+		pp.aperture = (float)atof(argv[idx + 1]);
+		focus_distance = atof(argv[idx + 2]);
+		if (!multipass)
+			pp.passes = 16;
+		multipass = lens = 1;
+	}
+	if ((idx = argv_find(argc, argv, "--target-error", 1))) {
+		pp.target_error = (float)atof(argv[idx + 1]);
+		multipass = 1;
+	}
+	if (multipass && ngpu > 1) {
+		LOG("--passes, --aa, --lens and --target-error render on one GPU, not on %d.", ngpu);
+		return 1;
+	}
 
 	LOG("Loading scene.");
 	const char *scale = NULL;
@@ -137,17 +177,40 @@ int main(int argc, char **argv)
 	for (int g = 0; g < ngpu; g++)
 		devs[g] = dev0 + g;
 	LOG("Commencing raytracing on %d GPU(s).", ngpu);
-	rtx_group *grp = NULL;
-	rtx_stats st;
-	if (rtx_group_open(ngpu, devs, &grp) || rtx_group_upload_scene(grp, desc) ||
-	    rtx_group_render(grp, &fr, &p, rgb, z) || rtx_group_get_stats(grp, &st)) {
-		LOG("%s", rtx_last_error());
+	rtx_stats st = { 0 };
+	uint64_t closest, shadow;
+	double kms;
+	if (multipass) {
+		/* one context on the first device: every pass through the render's own path, the mean saved */
+		if (lens)
+			pp.focus = (float)(focus_distance / (double)desc->camera.focal_length);
+		rtx_ctx *ctx = NULL;
+		rtx_pass_stats ps;
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, NULL) ||
+		    rtx_get_pass_stats(ctx, &ps)) {
+			LOG("%s", rtx_last_error());
+			rtx_close(ctx);
+			return 1;
+		}
+		rtx_close(ctx);
+		LOG("Passes: %u of %u run, error %.6g, render %.3f ms, accumulation %.3f ms.", ps.passes_run, pp.passes, ps.error,
+		    ps.render_ms, ps.accum_ms);
+		closest = ps.closest_rays;
+		shadow = ps.shadow_rays;
+		kms = ps.render_ms;
+	} else {
+		rtx_group *grp = NULL;
+		if (rtx_group_open(ngpu, devs, &grp) || rtx_group_upload_scene(grp, desc) ||
+		    rtx_group_render(grp, &fr, &p, rgb, z) || rtx_group_get_stats(grp, &st)) {
+			LOG("%s", rtx_last_error());
+			rtx_group_close(grp);
+			return 1;
+		}
 		rtx_group_close(grp);
-		return 1;
+		closest = st.closest_rays;
+		shadow = st.shadow_rays;
+		kms = st.kernel_ms;
 	}
-	rtx_group_close(grp);
-	const uint64_t closest = st.closest_rays, shadow = st.shadow_rays;
-	const double kms = st.kernel_ms;
 	if (ngpu > 1)
 		LOG("Gathered %d shards in %.3f ms.", ngpu, st.gather_ms);
 	LOG("Rays: %llu closest + %llu shadow in %.3f ms device time (%.1f Mrays/s).", (unsigned long long)closest,

@@ -416,6 +416,34 @@ class Renderer:
         _check(self.lib.rtx_get_denoise_stats(self._ctx, C.byref(s)))
         return s
 
+    def render_passes(self, frame, params, passes, jitter=False, aperture=0.0, focus=1.0, target_error=0.0, min_passes=2):
+        """rtx_render_passes on host arrays: the frame rendered `passes` times (seed + k; jitter: each pass at its own
+        sub-pixel offset; aperture > 0: a thin lens) and combined on the device.  Returns (rgb (h, w, 3) the mean,
+        z (h, w) pass 0's, variance (h, w, 3) of the mean); pass_stats() tells how many passes ran."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        _check(self.lib.rtx_render_passes(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), rgb.ctypes.data,
+                                          z.ctypes.data, var.ctypes.data))
+        return rgb, z, var
+
+    def render_passes_device(self, frame, params, passes, d_rgb, d_z, d_variance, stream=None, jitter=False, aperture=0.0,
+                             focus=1.0, target_error=0.0, min_passes=2):
+        """rtx_render_passes_device: d_rgb / d_z / d_variance are device pointers (ints, 16-byte aligned) or None;
+        stream: hipStream_t as int or None."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        _check(self.lib.rtx_render_passes_device(self._ctx, C.byref(frame), C.byref(params), C.byref(pp),
+                                                 C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                                 C.c_void_p(d_variance) if d_variance else None,
+                                                 C.c_void_p(stream) if stream else None))
+
+    def pass_stats(self):
+        s = abi.PassStats()
+        _check(self.lib.rtx_get_pass_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)
@@ -426,6 +454,27 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+def pass_params(jitter=None, **params):
+    """rtx_pass_params_default plus overrides (passes, flags, aperture, focus, target_error, min_passes); jitter
+    sets or clears RTX_PASS_JITTER in flags"""
+    p = abi.PassParams()
+    rtx_lib().rtx_pass_params_default(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    if jitter is not None:
+        p.flags = (p.flags | abi.RTX_PASS_JITTER) if jitter else (p.flags & ~abi.RTX_PASS_JITTER)
+    return p
+
+
+def pass_frame(frame, k, **params):
+    """rtx_pass_frame (no device needed): the frame of pass k of `frame` under pass_params(**params)"""
+    out = Frame()
+    _check(rtx_lib().rtx_pass_frame(C.byref(frame), C.byref(pass_params(**params)), k, C.byref(out)))
+    return out
 
 
 def tree_frame(scene):

@@ -198,6 +198,24 @@ FEATURE_DTYPE = [("position", "<f4", 3), ("z", "<f4"), ("normal", "<f4", 3), ("m
 # rtx_denoise_params_default
 DENOISE_DEFAULTS = {"iterations": 1, "sigma_color": 0.004, "sigma_normal": 0.05, "sigma_albedo": 0.1, "sigma_plane": 0.02}
 
+# multi-pass rendering (rtx_pass_frame, rtx_render_passes*)
+RTX_PASS_JITTER = 1
+RTX_PASSES_MAX = 65536
+
+
+class PassParams(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("aperture", C.c_float), ("focus", C.c_float),
+                ("target_error", C.c_float), ("min_passes", C.c_uint32)]
+
+
+class PassStats(C.Structure):
+    _fields_ = [("passes_run", C.c_uint32), ("pad_", C.c_uint32), ("error", C.c_double), ("render_ms", C.c_double),
+                ("accum_ms", C.c_double), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
+
+
+# rtx_pass_params_default
+PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
+
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
     KAT_MORTON, KAT_U32, KAT_GI_DIR, KAT_REFRACT, KAT_ANY_TRI, KAT_SPH_LIGHT_SH, KAT_BOX_Q, KAT_SPEC_POW, \
@@ -221,7 +239,9 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
                "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats",
                "rtx_frame_features_device", "rtx_frame_features", "rtx_denoise_params_default", "rtx_denoise_device",
-               "rtx_denoise", "rtx_get_denoise_stats"]
+               "rtx_denoise", "rtx_get_denoise_stats",
+               "rtx_pass_params_default", "rtx_pass_frame", "rtx_render_passes", "rtx_render_passes_device",
+               "rtx_get_pass_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -387,6 +407,18 @@ def declare_rtx(lib):
     lib.rtx_denoise.restype = C.c_int
     lib.rtx_get_denoise_stats.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
     lib.rtx_get_denoise_stats.restype = C.c_int
+    lib.rtx_pass_params_default.argtypes = [C.POINTER(PassParams)]
+    lib.rtx_pass_params_default.restype = None
+    lib.rtx_pass_frame.argtypes = [C.POINTER(Frame), C.POINTER(PassParams), C.c_uint32, C.POINTER(Frame)]
+    lib.rtx_pass_frame.restype = C.c_int
+    lib.rtx_render_passes.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams), C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
+    lib.rtx_render_passes.restype = C.c_int
+    lib.rtx_render_passes_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_passes_device.restype = C.c_int
+    lib.rtx_get_pass_stats.argtypes = [C.c_void_p, C.POINTER(PassStats)]
+    lib.rtx_get_pass_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

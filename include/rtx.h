@@ -663,6 +663,72 @@ typedef struct rtx_denoise_stats {
 int rtx_get_denoise_stats(const rtx_ctx *ctx, rtx_denoise_stats *out);
 
 /*
+ * Multi-pass rendering: the frame rendered K times and the passes combined on the device
+ * into a per-pixel mean and the variance of that mean.  Pass k has its own seed (params->seed + k), its own
+ * sub-pixel offset (anti-aliasing) and its own lens point (a thin lens).  k_trace forms a pixel's ray from
+ * nothing but the rtx_frame, so a jittered or thin-lens pass is just another rtx_frame: rtx_pass_frame
+ * returns it, and a pass is the frame rtx_render gives for that frame and seed, to the bit.
+ */
+enum { RTX_PASS_JITTER = 1 };            /* sub-pixel offsets (anti-aliasing) */
+#define RTX_PASSES_MAX 65536u
+typedef struct rtx_pass_params {
+	uint32_t passes;        /* 1..RTX_PASSES_MAX */
+	uint32_t flags;         /* RTX_PASS_JITTER or 0 */
+	float aperture;         /* lens radius in world units; 0 = pinhole (the default) */
+	float focus;            /* aperture > 0: the plane in focus is the image plane scaled about frame->origin
+	                         * by this (focus distance / camera focal_length), > 0 */
+	float target_error;     /* 0 = run every pass; > 0: stop after the first pass k+1 >= min_passes whose error
+	                         * (below) is <= target_error */
+	uint32_t min_passes;    /* 2..passes, read only when target_error > 0 */
+} rtx_pass_params;
+void rtx_pass_params_default(rtx_pass_params *p);   /* 1 pass, no flags, aperture 0, focus 1, target 0, min 2 */
+/*
+ * The frame of pass k (host only, no device needed).  With phi_b(k) the radical inverse of k in base b, every
+ * component evaluated in double from the float inputs and rounded to float once, width and height copied:
+ *   offset    (ox, oy) = (0, 0) for k = 0 or without RTX_PASS_JITTER, else (phi_2(k) - 1/2, phi_3(k) - 1/2);
+ *             cj = corner + ox step_x + oy step_y
+ *   pinhole   (aperture == 0): out = {cj, step_x, step_y, origin}; pass 0 is *frame bit for bit
+ *   thin lens (aperture > 0): L = origin for k = 0, else origin + aperture sqrt(phi_5(k)) (cos(2 pi phi_7(k)) x^
+ *             + sin(2 pi phi_7(k)) y^), x^ and y^ the unit vectors of step_x and step_y; out.origin = L,
+ *             out.corner = origin + focus (cj - origin), out.step_x = focus step_x, out.step_y = focus step_y:
+ *             the image plane moves to the plane in focus, so a pixel's rays from every lens point pass
+ *             through one focal point
+ * RTX_ERR_ARG: a null pointer, k >= passes, passes outside 1..RTX_PASSES_MAX, unknown flag bits, aperture < 0
+ * or NaN, aperture > 0 with focus <= 0 or not finite, target_error < 0 or NaN, min_passes outside 2..passes
+ * while target_error > 0, a zero-length step_x or step_y while aperture > 0.
+ */
+int rtx_pass_frame(const rtx_frame *frame, const rtx_pass_params *pp, uint32_t k, rtx_frame *out);
+/*
+ * Renders rtx_pass_frame(frame, pp, k) with params and seed + k (uint64 wrap) for k = 0 .. passes-1 through
+ * rtx_render_device's path and folds each pass into per-pixel, per-channel running state held in double
+ * (Welford: d = x - mean, mean += d / (k+1), m2 += d (x - mean)).  With n the number of passes run:
+ *   rgb[W*H*3]      = (float)mean
+ *   variance[W*H*3] = (float)(m2 / (n (n-1))) per channel, the variance OF THE MEAN; 0 when n = 1
+ *   z[W*H]          = pass 0's z (with a pinhole: rtx_render's z buffer bit for bit)
+ * HOST buffers; each may be NULL.  A non-finite pass value poisons that pixel's mean as the arithmetic does.
+ * The error E = sqrt(sum var_mean) / sum |mean|, both sums over the channels of the pixels whose mean is
+ * finite (0 if the denominator is 0), is a deterministic reduction (per-block partial sums in double, added
+ * in index order, no atomics): two runs stop after the same pass and return the same bits.
+ * params->tile_offset / tile_stride must be 0 / 1.  Errors as rtx_render (RTX_ERR_STATE before an upload),
+ * and every rtx_pass_frame error, raised before anything is launched.  rtx_get_stats afterwards describes the
+ * last pass.  Device groups have no such entry.
+ */
+int rtx_render_passes(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+		      float *rgb, float *z, float *variance);
+/* Same into DEVICE buffers (16-byte aligned, each may be NULL), enqueued on `stream` (NULL = the context's
+ * own); synchronises the stream. */
+int rtx_render_passes_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			     void *d_rgb, void *d_z, void *d_variance, void *stream);
+typedef struct rtx_pass_stats {   /* the last rtx_render_passes* of the context */
+	uint32_t passes_run, pad_;
+	double error;            /* the error after the last pass (0 after one pass) */
+	double render_ms;        /* sum of the passes' rtx_stats.kernel_ms */
+	double accum_ms;         /* the accumulation / error kernels, HIP events */
+	uint64_t closest_rays, shadow_rays;   /* summed over the passes */
+} rtx_pass_stats;
+int rtx_get_pass_stats(const rtx_ctx *ctx, rtx_pass_stats *out);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
