@@ -277,7 +277,7 @@ typedef struct DScene {
 } DScene;
 #define RTX_ORD_CAP 1024u                /* most samples of one emitter a point orders */
 #define RTX_ORD_BUCKETS 16u              /* buckets of the key */
-#define RTX_ORD_WORDS (4u * RTX_ORD_CAP) /* a wave's slice: order[CAP], then the results' x, y and z, CAP floats each */
+#define RTX_ORD_WORDS (4u * RTX_ORD_CAP) /* a wave's slice: order[CAP], then one 12-byte result record (x, y, z) per sample */
 #define RTX_CULL_MAX 64
 
 /* k_trace keeps the first RTX_TRACE_LSTK entries of a lane's closest-hit stack in LDS and the

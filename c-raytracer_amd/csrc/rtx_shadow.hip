@@ -42,7 +42,9 @@
 #include "rtx_launch.h"
 
 #ifndef RTX_DEBUG_NOWALK
-#define RTX_DEBUG_NOWALK 0 /* measurement only: skip the BVH walk (everything else in k_shadow stays) */
+#define RTX_DEBUG_NOWALK 0 /* measurement only: skip the BVH walk (everything else in k_shadow stays); 2: the walking
+                            * points' runs are still ordered (order_begin, the order reads, the result slots), 1: they
+                            * become all-clear points */
 #endif
 #ifndef RTX_DEBUG_NOLEAF
 #define RTX_DEBUG_NOLEAF 0 /* measurement only: the walk tests no leaf (wrong images; the cost of the leaf tests) */
@@ -1569,13 +1571,17 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
  * on the axis, across the world axis the cone axis is least along).  Dark samples (sample_dark)
  * get no place in the order: they are never walked.
  *   The key pass runs the packets in index order: each lane forms its sample as light_sample does
- * (emitter_sample, sample_att, sample_dark: the same operations, so the same dark lanes), stores
- * the bucket in its result slot and counts the buckets (lane b holds bucket b's count).  A second
- * pass ranks every sample inside its bucket (ballot and mbcnt: stable in the index) and stores
- * order[pos] = index - base, then zeroes the result slots.  The caller walks the packets of
+ * (emitter_sample, sample_att, sample_dark: the same operations, so the same dark lanes), keeps
+ * the bucket in registers (a run has at most 16 packets: 4 bits a packet and a "placed" bit) and
+ * counts the buckets (lane b holds bucket b's count).  A second pass ranks every sample inside its
+ * bucket from ballots of the bucket's bits (order_bits, order_same: stable in the index), stores
+ * order[pos] = index - base, and zeroes the result slots of the samples without a place: a placed
+ * sample's slot is stored after its walk, blocked or not.  The caller walks the packets of
  * positions [64 k, 64 k + 64), stores each contribution at its sample's result slot and adds the
  * slots in index order, lane l taking l, 64 + l, ..: the additions today's loop makes, in its order.
- *   ob: the wave's slice of KShadow.ord.  Returns 0 (the run is not ordered: today's packets), or
+ *   ob: the wave's slice of KShadow.ord: order[RTX_ORD_CAP], then the samples' result records, 12
+ * bytes (x, y, z) each, one store and one load a sample.  Nothing in a slice outlives its run, so
+ * it is never cleared.  Returns 0 (the run is not ordered: today's packets), or
  * bit 31 | packets of the run << 16 | samples in the order.  (KAT: RTX_KAT_ORDER) */
 __device__ __forceinline__ uint32_t order_bucket(float x)
 {
@@ -1611,6 +1617,52 @@ __device__ __forceinline__ uint32_t order_key(const KShadow &ks, const float4 *r
 	if (xo)
 		*xo = x;
 	return act && !dark ? order_bucket(x) : RTX_ORD_BUCKETS;
+}
+/* sample jr's result record in the wave's slice ob: 12 bytes after the order's words, one store and
+ * one load (global_*_dwordx3; the values through VGPRs formed here, or the zeroes of order_begin
+ * are hoisted to the kernel's entry and spilled) */
+__device__ __forceinline__ void order_slot_put(uint32_t *ob, uint32_t jr, f3 v)
+{
+	auto *r = gptrw((float *)ob + RTX_ORD_CAP + 3u * jr);
+	asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z));
+	r[0] = v.x;
+	r[1] = v.y;
+	r[2] = v.z;
+}
+__device__ __forceinline__ f3 order_slot_get(const uint32_t *ob, uint32_t jr)
+{
+	const auto *r = gptr((const float *)ob + RTX_ORD_CAP + 3u * jr);
+	return mk3(r[0], r[1], r[2]);
+}
+/* One packet's buckets as lane masks: word b < 4 has the lanes whose bucket has bit b set, word 4 the
+ * lanes with a place in the order.  The words are copied to VGPRs once, so what order_same does with
+ * them has no scalar operand (any SGPR operand halves the VALU issue rate, bench.py's header). */
+struct OrderBits {
+	uint32_t lo[5], hi[5];
+};
+__device__ __forceinline__ void order_bits(uint32_t bk, OrderBits &o)
+{
+	for (uint32_t k = 0; k < 5; k++) {
+		const u64 m = ballot(k < 4 ? ((bk >> k) & 1u) != 0u : bk < RTX_ORD_BUCKETS);
+		o.lo[k] = (uint32_t)m;
+		o.hi[k] = (uint32_t)(m >> 32);
+		asm volatile("" : "+v"(o.lo[k]), "+v"(o.hi[k]));
+	}
+}
+/* the packet's placed samples of bucket sel & 15 (sel per lane): the AND over the key's bits of
+ * (bit set ? B_b : ~B_b), and the placed lanes.  Returns their number; *below: those in lanes below
+ * this one, a sample's rank among its packet's samples of its bucket (stable in the index) */
+__device__ __forceinline__ uint32_t order_same(const OrderBits &o, uint32_t sel, uint32_t *below)
+{
+	uint32_t lo = o.lo[4], hi = o.hi[4];
+	for (uint32_t k = 0; k < 4; k++) {
+		const uint32_t inv = ((sel >> k) & 1u) - 1u; /* all ones where the bit is clear */
+		lo &= o.lo[k] ^ inv;
+		hi &= o.hi[k] ^ inv;
+	}
+	if (below)
+		*below = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+	return (uint32_t)__popc(lo) + (uint32_t)__popc(hi);
 }
 template <bool COUNT, int WALK>
 __device__ __forceinline__ uint32_t order_begin(const KShadow &ks, const float4 *rec, uint32_t nl, uint32_t base, const uint32_t *cmask,
@@ -1654,19 +1706,21 @@ __device__ __forceinline__ uint32_t order_begin(const KShadow &ks, const float4 
 	const f3 b = order_dir(p, lc, mk3(ks.tf.c[0] + ks.tf.cf[0], ks.tf.c[1] + ks.tf.cf[1], ks.tf.c[2] + ks.tf.cf[2]));
 	const float ilr = lr > 0.f ? 1.f / lr : 0.f;
 	const bool dk_on = uni(ks.dark) != 0;
-	uint32_t *ord = ob;
-	uint32_t *rx = ob + RTX_ORD_CAP, *ry = ob + 2 * RTX_ORD_CAP, *rz = ob + 3 * RTX_ORD_CAP;
-	uint32_t cnt = 0; /* lane b: the samples of bucket b */
+	auto *ord = gptrw(ob);
+	/* the lane's buckets of the run's packets: 4 bits a packet, and a bit a packet for "has a place" */
+	u64 bks = 0;
+	uint32_t plc = 0;
+	uint32_t cnt = 0; /* lane l: the samples of bucket l & 15 */
 	for (uint32_t m = 0; m < npk; m++) {
-		const uint32_t jr = m * WAVE + lane_id(), idx = base + jr;
+		const uint32_t idx = base + m * WAVE + lane_id();
 		const bool act = idx < rend;
 		bool dark;
 		const uint32_t bk = order_key(ks, rec, Eu, e, idx - start, __float_as_uint(q4.y), __float_as_uint(q4.z), p, b, ilr, dk_on, act, dark);
-		rx[jr] = bk;
-		for (uint32_t k = 0; k < RTX_ORD_BUCKETS; k++) {
-			const uint32_t c = popc64(ballot(bk == k));
-			cnt += lane_id() == k ? c : 0u;
-		}
+		bks |= (u64)(bk & (RTX_ORD_BUCKETS - 1u)) << (4u * m);
+		plc |= (bk < RTX_ORD_BUCKETS ? 1u : 0u) << m;
+		OrderBits ob5;
+		order_bits(bk, ob5);
+		cnt += order_same(ob5, lane_id(), nullptr);
 		if (COUNT) { /* what light_sample counts for the dark lanes of this packet in index order */
 			const uint32_t na = popc64(ballot(act)), nd = popc64(ballot(act && dark));
 			sc.dark += nd;
@@ -1677,25 +1731,22 @@ __device__ __forceinline__ uint32_t order_begin(const KShadow &ks, const float4 
 		}
 	}
 	uint32_t total;
-	uint32_t first = wave_excl_scan(cnt, &total); /* lane b: the first position of bucket b */
+	uint32_t first = wave_excl_scan(lane_id() < RTX_ORD_BUCKETS ? cnt : 0u, &total); /* lane b < 16: the first position of bucket b */
 	for (uint32_t m = 0; m < npk; m++) {
 		const uint32_t jr = m * WAVE + lane_id();
-		const uint32_t bk = rx[jr];
-		uint32_t pos = 0;
-		for (uint32_t k = 0; k < RTX_ORD_BUCKETS; k++) {
-			const u64 mk = ballot(bk == k);
-			if (!mk)
-				continue;
-			const uint32_t f = readlane(first, k);
-			if (bk == k)
-				pos = f + mbcnt(mk);
-			first += lane_id() == k ? popc64(mk) : 0u;
-		}
-		if (bk < RTX_ORD_BUCKETS)
-			ord[pos] = jr;
-		rx[jr] = 0u; /* +0.f: what a dark or idle sample adds */
-		ry[jr] = 0u;
-		rz[jr] = 0u;
+		const bool placed = (plc >> m) & 1u;
+		const uint32_t bk = placed ? (uint32_t)(bks >> (4u * m)) & (RTX_ORD_BUCKETS - 1u) : RTX_ORD_BUCKETS;
+		OrderBits ob5;
+		order_bits(bk, ob5);
+		uint32_t rank;
+		order_same(ob5, bk, &rank);
+		/* the bucket's first free position, from the lane that holds it (a sample without a place reads lane 16) */
+		const uint32_t f = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(bk << 2), (int)first);
+		first += order_same(ob5, lane_id(), nullptr);
+		if (placed)
+			ord[f + rank] = jr;
+		else
+			order_slot_put(ob, jr, mk3(0.f, 0.f, 0.f)); /* +0.f: what a dark or idle sample adds; a placed one's lane stores after its walk */
 	}
 	lds_sync(); /* the order and the zeroed slots, before other lanes read and write them */
 	if (COUNT) {
@@ -1819,7 +1870,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 					 * cone, planes, listed objects and sampled emitters (at most 8 emitters), handed over
 					 * as point_masks' are below.  The smp byte is 0 for a far point only */
 					const uint32_t w = cptr(pm)[uni(sid[k])];
-					const bool tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK;
+					const bool tree = uni(ks.have_tree) != 0 && RTX_DEBUG_NOWALK != 1;
 					const uint32_t smp = w >> 24, ok = (w >> 8) & (w >> 16) & (tree ? w : ~0u) & 0xffu;
 					const bool ac = uni(ks.point) != 0 && smp && !(smp & ~ok);
 					if (lane_id() == 0) {
@@ -1848,7 +1899,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						m = point_masks(ks, pu, ou & ~RTX_SP_FAR, (ou & RTX_SP_FAR) != 0);
 					/* all-clear: every emitter the point samples is clear of the tree (or there is none),
 					 * the planes and the listed records */
-					const bool tree = uni(ks.have_tree) != 0 && !RTX_DEBUG_NOWALK;
+					const bool tree = uni(ks.have_tree) != 0 && RTX_DEBUG_NOWALK != 1;
 					const u64 ok = m.pln & m.lin & (tree ? m.cone : ~0ull);
 					const bool ac = uni(ks.point) != 0 && !(ou & RTX_SP_FAR) && uni(ks.num_emitters) <= 64u && !(m.smp & ~ok);
 					if (lane_id() == 0) {
@@ -1886,7 +1937,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						uint32_t *ob = unip(ks.ord);
 						if (ob)
 							ob += (size_t)(blockIdx.x * RTX_SH_NW + wv) * RTX_ORD_WORDS;
-						if (!st && ob && uni(ks.have_tree) && !RTX_DEBUG_NOWALK && !uni(wt_w[wv].cm[6])) {
+						if (!st && ob && uni(ks.have_tree) && RTX_DEBUG_NOWALK != 1 && !uni(wt_w[wv].cm[6])) {
 							st = order_begin<COUNT, WALK>(ks, rec, nl, base, wt_w[wv].cm, ob, sc);
 							if (st && !(st & 0x7ffu)) {
 								/* every sample dark: nothing to walk, and the slots' +0 leave acc as it is
@@ -1903,7 +1954,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 						if (st) {
 							const uint32_t pos = ((st >> 11) & 31u) * WAVE + lane_id();
 							act = pos < (st & 0x7ffu);
-							idx = base + (act ? ob[pos] : 0u);
+							idx = base + (act ? gptr(ob)[pos] : 0u);
 						}
 					}
 					const f3 contribution = light_sample<COUNT, WALK, true, LA, false, DK>(ks, rec, 0u, idx, act, sc, top_q, top_e, stk, t8,
@@ -1918,18 +1969,14 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 							const uint32_t pk = (st >> 11) & 31u, npk = (st >> 16) & 31u, no = st & 0x7ffu;
 							const uint32_t pos = pk * WAVE + lane_id();
 							if (pos < no) {
-								const uint32_t jr = ob[pos];
-								ob[RTX_ORD_CAP + jr] = __float_as_uint(contribution.x);
-								ob[2 * RTX_ORD_CAP + jr] = __float_as_uint(contribution.y);
-								ob[3 * RTX_ORD_CAP + jr] = __float_as_uint(contribution.z);
+								order_slot_put(ob, gptr(ob)[pos], contribution);
 							}
 							const bool last = (pk + 1) * WAVE >= no;
 							if (last) {
 								lds_sync(); /* every lane's results, before the lanes that add them */
 								for (uint32_t m = 0; m < npk; m++) {
 									const uint32_t jr = m * WAVE + lane_id();
-									acc = add3(acc, mk3(__uint_as_float(ob[RTX_ORD_CAP + jr]), __uint_as_float(ob[2 * RTX_ORD_CAP + jr]),
-											    __uint_as_float(ob[3 * RTX_ORD_CAP + jr])));
+									acc = add3(acc, order_slot_get(ob, jr));
 								}
 								base += npk * WAVE;
 							}
