@@ -2,7 +2,7 @@
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
  * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
- * rtx_passes.cpp (multi-pass rendering) and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
+ * rtx_passes.cpp (multi-pass rendering, adaptive passes) and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
@@ -214,6 +214,16 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<double> d_pass_sums;   /* the blocks' partial sums of the error, then their two totals */
 	DevBuf<float> d_pass_var;     /* the host-buffer call's device copy of the variance */
 	rtx_pass_stats pass_stats{};
+	/* tile-list renders (rtx_render_tiles*) */
+	DevBuf<uint32_t> d_tile_list; /* the host-buffer call's device copy of the list */
+	DevBuf<uint32_t> d_tile_flag; /* the device call's list check raises it */
+	/* adaptive passes (rtx_render_adaptive*): grow-only scratch of its own, rtx_adaptive.hip */
+	DevBuf<double> d_ad_state;    /* mean r, g, b and m2 r, g, b, tile-major planes of 64 T doubles */
+	DevBuf<double> d_ad_vs;       /* V_t then S_t per tile, then the pass's totals V and A */
+	DevBuf<uint32_t> d_ad_tiles;  /* n_t per tile, the two pass lists in turn, the next list's count */
+	DevBuf<float> d_ad_var;       /* the host-buffer call's device copies */
+	DevBuf<uint32_t> d_ad_passes;
+	rtx_adaptive_stats ad_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;
@@ -313,8 +323,10 @@ int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take);
 uint32_t rtx_wide8_build(const std::vector<DNode> &inner, uint32_t nnodes, const DPrim *prims, uint32_t root_ref,
 			 const float lo[3], const float hi[3], const std::vector<uint32_t> &skip_objs, const DTreeFrame &tf,
 			 double fpad, QFrame &F, bool &skipped, std::vector<DW8> &out, std::vector<uint32_t> &leafmap);
-/* one frame (or tile shard) into device buffers on stream */
-int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z, hipStream_t stream);
+/* one frame (or tile shard) into device buffers on stream.  d_tiles: a checked device list of n_tiles tile indices
+ * (strictly increasing, below the frame's tile count) to render instead, with tile sharding 0/1 */
+int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z, hipStream_t stream,
+		      const uint32_t *d_tiles = nullptr, uint32_t n_tiles = 0);
 /* rtx_scene.cpp: c's scene buffers freed (c's device current) */
 RTX_HIDDEN void rtx_free_scene(rtx_ctx *c);
 /* rtx_query.cpp: n checked rays on device buffers into c->ray_stats (the feature buffers' query too) */

@@ -50,15 +50,16 @@ hipError_t rtx_w8_collapse_device(const DNode *recs, uint32_t nnodes, uint32_t n
 				  uint32_t *top_out, float qo[3], float qs[3], hipStream_t st);
 RTX_HIDDEN hipError_t rtx_load_wide8_dev(void);
 
-/* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays */
+/* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays.  tile_list: the device list of a tile-list render
+ * (rtx_render_tiles*), indexed by the chunk positions tile_begin..; null: the shard of P */
 size_t rtx_trace_lds_bytes(uint32_t stack_size);
 hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu);
 hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const DParams *P, float *rgb, float *z, DTask *tasks,
 			    uint32_t task_cap, float4 *staging, uint32_t staging_cap, float4 *sp_out, uint32_t sp_cap,
 			    uint2 *tile_rec, uint32_t tile_begin, uint32_t tile_end, unsigned long long *ctr, uint32_t waves,
-			    int count, hipStream_t stream);
+			    int count, const uint32_t *tile_list, hipStream_t stream);
 hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec, const float4 *contrib,
-			    uint32_t tile_begin, uint32_t ntiles, float *rgb, hipStream_t stream);
+			    uint32_t tile_begin, uint32_t ntiles, float *rgb, const uint32_t *tile_list, hipStream_t stream);
 size_t rtx_rays_lds_bytes(uint32_t stack_size);
 hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu);
 hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
@@ -115,6 +116,18 @@ RTX_HIDDEN uint32_t rtx_pass_blocks(uint64_t n);
 RTX_HIDDEN hipError_t rtx_launch_pass_fold(uint64_t n, uint32_t k, int out, const float *rgb, double *state, float *out_rgb,
 					   float *out_var, double *partials, double *sums, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_passes(void);
+
+/* rtx_adaptive.hip: a device tile list's check, and the per-tile state of rtx_render_adaptive* */
+RTX_HIDDEN hipError_t rtx_launch_tiles_check(const uint32_t *tiles, uint32_t n, uint32_t total, uint32_t *flag, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_tile_all(uint32_t total, uint32_t *list, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_tile_fold(uint32_t w, uint32_t h, uint32_t k, const uint32_t *list, uint32_t n_list,
+					   const float *rgb, double *state, uint32_t *count, double *vs, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_tile_select(uint32_t total, uint32_t k, uint32_t min_passes, float target,
+					     const uint32_t *count, const double *vs, uint32_t *next, uint32_t *n_next,
+					     double *sums, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_tile_out(uint32_t w, uint32_t h, const double *state, const uint32_t *count, float *rgb,
+					  float *var, uint32_t *tile_passes, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_adaptive(void);
 
 }
 

@@ -1,7 +1,8 @@
 /*
  * C-ABI of include/rtx.h, multi-pass rendering: the frame of pass k (host only), and the frame
  * rendered pass by pass through the render's own path, each pass folded on the device into a per-pixel mean
- * and the variance of that mean (rtx_passes.hip).
+ * and the variance of that mean (rtx_passes.hip); and adaptive passes, in which each pass renders the tiles still
+ * over their share of the error budget through the tile-list path (rtx_adaptive.hip).
  */
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include "rtx.h"
 #include "rtx_device.h"
 #include "rtx_internal.h"
+#include "rtx_tiles.h"
 
 extern "C" void rtx_pass_params_default(rtx_pass_params *p)
 {
@@ -204,5 +206,119 @@ extern "C" int rtx_render_passes(rtx_ctx *c, const rtx_frame *fr, const rtx_para
 		HIP_TRY(hipMemcpy(z, c->d_z, px * 4, hipMemcpyDeviceToHost));
 	if (variance)
 		HIP_TRY(hipMemcpy(variance, c->d_pass_var, px * 12, hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
+/* everything rtx_render_adaptive* refuses before it launches anything */
+static int adaptive_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp)
+{
+	int rc = passes_check(c, fr, p, pp);
+	if (rc)
+		return rc;
+	if (!(pp->target_error > 0.f))
+		return fail(RTX_ERR_ARG, "adaptive passes need a target error above 0");
+	if (rtx_tiles_total(fr->width, fr->height) > (1ull << 26))
+		return fail(RTX_ERR_ARG, "frame %ux%u has more than 2^26 tiles", fr->width, fr->height);
+	return RTX_OK;
+}
+
+/* checked arguments, device outputs (each may be null) */
+static int adaptive_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, float *d_rgb, float *d_z,
+			   float *d_var, uint32_t *d_tile_passes, hipStream_t stream)
+{
+	const uint64_t n = (uint64_t)fr->width * fr->height;
+	const uint32_t T = (uint32_t)rtx_tiles_total(fr->width, fr->height);
+	/* d_ad_tiles: n_t per tile | list A | list B | the next list's count;  d_ad_vs: V_t | S_t | V, A */
+	if (c->d_pass_rgb.grow(n * 3 * sizeof(float)) != hipSuccess || c->d_ad_state.grow((size_t)T * 64 * 6 * sizeof(double)) != hipSuccess ||
+	    c->d_ad_vs.grow(((size_t)T * 2 + 2) * sizeof(double)) != hipSuccess ||
+	    c->d_ad_tiles.grow(((size_t)T * 3 + 1) * sizeof(uint32_t)) != hipSuccess)
+		return fail(RTX_ERR_NOMEM, "adaptive pass state of %u tiles", T);
+	uint32_t *count = c->d_ad_tiles, *list = count + T, *next = list + T, *d_n_next = next + T;
+	double *vs = c->d_ad_vs, *d_sums = vs + (size_t)T * 2;
+	rtx_adaptive_stats as{};
+	as.tiles = T;
+	uint32_t active = T;
+	HIP_TRY(rtx_launch_tile_all(T, list, stream));
+	for (uint32_t k = 0; k < pp->passes && active; k++) {
+		rtx_frame fk;
+		int rc = rtx_pass_frame(fr, pp, k, &fk);
+		if (rc)
+			return rc;
+		rtx_params pk = *p;
+		pk.seed = p->seed + k;
+		rc = rtx_render_common(c, &fk, &pk, c->d_pass_rgb, k == 0 ? d_z : nullptr, stream, list, active);
+		if (rc)
+			return rc;
+		as.render_ms += c->stats.kernel_ms;
+		as.closest_rays += c->stats.closest_rays;
+		as.shadow_rays += c->stats.shadow_rays;
+		as.tile_passes += active;
+		as.passes_run = k + 1;
+		HIP_TRY(hipEventRecord(c->ev0, stream));
+		HIP_TRY(rtx_launch_tile_fold(fr->width, fr->height, k, list, active, c->d_pass_rgb, c->d_ad_state, count, vs, stream));
+		HIP_TRY(rtx_launch_tile_select(T, k, pp->min_passes, pp->target_error, count, vs, next, d_n_next, d_sums, stream));
+		HIP_TRY(hipEventRecord(c->ev1, stream));
+		/* the next list's length and the two totals: the pass's one read, on the sync it needs anyway */
+		double sums[2] = { 0.0, 0.0 };
+		uint32_t n_next = 0;
+		HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&n_next, d_n_next, sizeof(n_next), hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+		as.fold_ms += ms;
+		as.error = sums[1] != 0.0 ? sqrt(sums[0]) / sums[1] : 0.0;
+		active = n_next;
+		std::swap(list, next);
+	}
+	HIP_TRY(hipEventRecord(c->ev0, stream));
+	HIP_TRY(rtx_launch_tile_out(fr->width, fr->height, c->d_ad_state, count, d_rgb, d_var, d_tile_passes, stream));
+	HIP_TRY(hipEventRecord(c->ev1, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+	as.fold_ms += ms;
+	c->ad_stats = as;
+	return RTX_OK;
+}
+
+extern "C" int rtx_render_adaptive_device(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, void *d_rgb,
+					  void *d_z, void *d_variance, void *d_tile_passes, void *stream)
+{
+	int rc = adaptive_check(c, fr, p, pp);
+	if (rc)
+		return rc;
+	if (((uintptr_t)d_rgb | (uintptr_t)d_z | (uintptr_t)d_variance | (uintptr_t)d_tile_passes) & 15u)
+		return fail(RTX_ERR_ARG, "output buffers must be 16-byte aligned");
+	HIP_TRY(hipSetDevice(c->device));
+	return adaptive_common(c, fr, p, pp, (float *)d_rgb, (float *)d_z, (float *)d_variance, (uint32_t *)d_tile_passes,
+			       stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int rtx_render_adaptive(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, float *rgb, float *z,
+				   float *variance, uint32_t *tile_passes)
+{
+	int rc = adaptive_check(c, fr, p, pp);
+	if (rc)
+		return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t px = (size_t)fr->width * fr->height;
+	const size_t T = (size_t)rtx_tiles_total(fr->width, fr->height);
+	HIP_TRY(rtx_ensure_framebuffer(c, px));
+	if ((variance && c->d_ad_var.grow(px * 3 * sizeof(float)) != hipSuccess) ||
+	    (tile_passes && c->d_ad_passes.grow(T * sizeof(uint32_t)) != hipSuccess))
+		return fail(RTX_ERR_NOMEM, "device copies of the variance and the pass counts of %zu pixels", px);
+	rc = adaptive_common(c, fr, p, pp, rgb ? c->d_rgb.p : nullptr, z ? c->d_z.p : nullptr, variance ? c->d_ad_var.p : nullptr,
+			     tile_passes ? c->d_ad_passes.p : nullptr, c->stream);
+	if (rc)
+		return rc;
+	if (rgb)
+		HIP_TRY(hipMemcpy(rgb, c->d_rgb, px * 12, hipMemcpyDeviceToHost));
+	if (z)
+		HIP_TRY(hipMemcpy(z, c->d_z, px * 4, hipMemcpyDeviceToHost));
+	if (variance)
+		HIP_TRY(hipMemcpy(variance, c->d_ad_var, px * 12, hipMemcpyDeviceToHost));
+	if (tile_passes)
+		HIP_TRY(hipMemcpy(tile_passes, c->d_ad_passes, T * 4, hipMemcpyDeviceToHost));
 	return RTX_OK;
 }

@@ -1,7 +1,7 @@
 /*
  * C-ABI of include/rtx.h, the render (replaces render_init + render, render.c:61-116 / 345-368):
- * a frame or tile shard in chunks of tiles through k_trace, the shade-point sort, k_shadow and
- * k_accum, and its statistics.
+ * a frame, a tile shard or a caller's list of tiles (rtx_render_tiles*) in chunks of tiles through k_trace,
+ * the shade-point sort, k_shadow and k_accum, and its statistics.
  */
 #include <hip/hip_runtime.h>
 
@@ -12,9 +12,10 @@
 #include "rtx.h"
 #include "rtx_device.h"
 #include "rtx_internal.h"
+#include "rtx_tiles.h"
 
 int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z,
-			 hipStream_t stream)
+			 hipStream_t stream, const uint32_t *d_tiles, uint32_t n_tiles)
 {
 	if (!c->have_scene)
 		return fail(RTX_ERR_STATE, "rtx_render before rtx_upload_scene");
@@ -24,6 +25,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		return fail(RTX_ERR_ARG, "empty frame %ux%u", fr->width, fr->height);
 	if (!p->tile_stride || p->tile_offset >= p->tile_stride)
 		return fail(RTX_ERR_ARG, "bad tile sharding %u/%u", p->tile_offset, p->tile_stride);
+	if (d_tiles && (p->tile_offset != 0 || p->tile_stride != 1))
+		return fail(RTX_ERR_ARG, "a tile list takes no tile sharding: %u/%u is not 0/1", p->tile_offset, p->tile_stride);
 	const DFrame F = rtx_dframe(fr);
 	DParams P;
 	memset(&P, 0, sizeof(P));
@@ -43,6 +46,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	const uint64_t tiles_y = (fr->height + RTX_TILE_H - 1) / RTX_TILE_H;
 	const uint64_t total = (uint64_t)P.tiles_x * tiles_y;
 	P.ntiles = p->tile_offset < total ? (uint32_t)((total - p->tile_offset + p->tile_stride - 1) / p->tile_stride) : 0;
+	if (d_tiles) /* a tile list (checked by the caller): the chunks run over list positions */
+		P.ntiles = n_tiles;
 
 	int per_cu = 0;
 	HIP_TRY(rtx_trace_occupancy(c->scene.stack_size, &per_cu));
@@ -138,7 +143,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		HIP_TRY(hipEventRecord(c->ev[0], stream));
 		HIP_TRY(rtx_launch_trace(&c->scene, &F, &P, d_rgb, d_z, c->d_tasks, task_cap, c->d_staging,
 					 (uint32_t)staging_cap, c->d_sp, sp_cap, c->d_tile_rec, begin, end, c->d_ctr,
-					 std::min<uint32_t>(waves, end - begin), p->count_traversal, stream));
+					 std::min<uint32_t>(waves, end - begin), p->count_traversal, d_tiles, stream));
 		HIP_TRY(hipEventRecord(c->ev[1], stream));
 		unsigned long long head[RTX_C_N];
 		HIP_TRY(hipMemcpyAsync(head, c->d_ctr, sizeof(head), hipMemcpyDeviceToHost, stream));
@@ -204,7 +209,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		if (premasked)
 			premask_points += n_sp;
 		HIP_TRY(hipEventRecord(c->ev[2], stream));
-		HIP_TRY(rtx_launch_accum(&F, &P, c->d_tile_rec, c->d_contrib, begin, end - begin, d_rgb, stream));
+		HIP_TRY(rtx_launch_accum(&F, &P, c->d_tile_rec, c->d_contrib, begin, end - begin, d_rgb, d_tiles, stream));
 		HIP_TRY(hipEventRecord(c->ev[3], stream));
 		unsigned long long ctr[RTX_C_N];
 		HIP_TRY(hipMemcpyAsync(ctr, c->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
@@ -229,7 +234,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	}
 	HIP_TRY(hipEventRecord(c->ev1, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
-	if (P.ntiles) {
+	/* a list render reads the estimate (the whole frame's settings key it) and leaves it as it is */
+	if (P.ntiles && !d_tiles) {
 		c->sp_tile_seen = (double)shade_points / P.ntiles;
 		c->sp_tile_key = sp_key;
 	}
@@ -299,6 +305,110 @@ extern "C" int rtx_render(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, 
 			HIP_TRY(hipMemcpyAsync(c->d_z, z, px * 4, hipMemcpyHostToDevice, c->stream));
 	}
 	int rc = rtx_render_common(c, fr, p, rgb ? c->d_rgb : nullptr, z ? c->d_z : nullptr, c->stream);
+	if (rc)
+		return rc;
+	if (rgb)
+		HIP_TRY(hipMemcpy(rgb, c->d_rgb, px * 12, hipMemcpyDeviceToHost));
+	if (z)
+		HIP_TRY(hipMemcpy(z, c->d_z, px * 4, hipMemcpyDeviceToHost));
+	return RTX_OK;
+}
+
+/* a host tile list: strictly increasing, every index below the frame's tile count */
+static int tile_list_check(const rtx_frame *fr, const uint32_t *tiles, uint32_t n_tiles)
+{
+	const uint64_t total = rtx_tiles_total(fr->width, fr->height);
+	for (uint32_t i = 0; i < n_tiles; i++) {
+		if (tiles[i] >= total)
+			return fail(RTX_ERR_ARG, "tile list entry %u: tile %u of %llu", i, tiles[i], (unsigned long long)total);
+		if (i && tiles[i - 1] >= tiles[i])
+			return fail(RTX_ERR_ARG, "tile list entry %u: %u after %u is not strictly increasing", i, tiles[i], tiles[i - 1]);
+	}
+	return RTX_OK;
+}
+
+/* what both tile-list entries refuse before they look at the list */
+static int tiles_args_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const void *tiles, uint32_t n_tiles)
+{
+	if (!c || !fr || !p)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (!c->have_scene)
+		return fail(RTX_ERR_STATE, "rtx_render_tiles before rtx_upload_scene");
+	if (!fr->width || !fr->height)
+		return fail(RTX_ERR_ARG, "empty frame %ux%u", fr->width, fr->height);
+	if (p->tile_offset != 0 || p->tile_stride != 1)
+		return fail(RTX_ERR_ARG, "a tile list takes no tile sharding: %u/%u is not 0/1", p->tile_offset, p->tile_stride);
+	if (n_tiles && !tiles)
+		return fail(RTX_ERR_ARG, "null tile list of %u tiles", n_tiles);
+	if (n_tiles > rtx_tiles_total(fr->width, fr->height))
+		return fail(RTX_ERR_ARG, "%u tiles listed of a frame of %llu", n_tiles,
+			    (unsigned long long)rtx_tiles_total(fr->width, fr->height));
+	return RTX_OK;
+}
+
+/* no tile: nothing is launched, and the statistics describe a render of nothing */
+static int render_no_tiles(rtx_ctx *c)
+{
+	const uint32_t walk = c->stats.trace_walk;
+	c->stats = rtx_stats{};
+	c->stats.trace_walk = walk;
+	c->pstats = rtx_point_stats{};
+	c->dstats = rtx_dark_stats{};
+	c->ostats = rtx_order_stats{};
+	c->mstats = rtx_premask_stats{};
+	return RTX_OK;
+}
+
+extern "C" int rtx_render_tiles_device(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const void *d_tiles, uint32_t n_tiles,
+				       void *d_rgb, void *d_z, void *stream)
+{
+	int rc = tiles_args_check(c, fr, p, d_tiles, n_tiles);
+	if (rc)
+		return rc;
+	if ((uintptr_t)d_tiles & 3u)
+		return fail(RTX_ERR_ARG, "the tile list must be 4-byte aligned");
+	if (!n_tiles)
+		return render_no_tiles(c);
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+	/* one lane per entry raises a flag word, read back before anything else is launched */
+	HIP_TRY(c->d_tile_flag.grow(sizeof(uint32_t)));
+	HIP_TRY(hipMemsetAsync(c->d_tile_flag, 0, sizeof(uint32_t), st));
+	HIP_TRY(rtx_launch_tiles_check((const uint32_t *)d_tiles, n_tiles, (uint32_t)rtx_tiles_total(fr->width, fr->height),
+				       c->d_tile_flag, st));
+	uint32_t flag = 0;
+	HIP_TRY(hipMemcpyAsync(&flag, c->d_tile_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	if (flag)
+		return fail(RTX_ERR_ARG, "the tile list is not strictly increasing below the frame's %llu tiles",
+			    (unsigned long long)rtx_tiles_total(fr->width, fr->height));
+	return rtx_render_common(c, fr, p, (float *)d_rgb, (float *)d_z, st, (const uint32_t *)d_tiles, n_tiles);
+}
+
+extern "C" int rtx_render_tiles(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const uint32_t *tiles, uint32_t n_tiles,
+				float *rgb, float *z)
+{
+	int rc = tiles_args_check(c, fr, p, tiles, n_tiles);
+	if (rc)
+		return rc;
+	rc = tile_list_check(fr, tiles, n_tiles);
+	if (rc)
+		return rc;
+	if (!n_tiles)
+		return render_no_tiles(c);
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t px = (size_t)fr->width * fr->height;
+	HIP_TRY(rtx_ensure_framebuffer(c, px));
+	HIP_TRY(c->d_tile_list.grow((size_t)n_tiles * sizeof(uint32_t)));
+	HIP_TRY(hipMemcpyAsync(c->d_tile_list, tiles, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	/* pixels of tiles outside the list keep the caller's values */
+	if (n_tiles < rtx_tiles_total(fr->width, fr->height)) {
+		if (rgb)
+			HIP_TRY(hipMemcpyAsync(c->d_rgb, rgb, px * 12, hipMemcpyHostToDevice, c->stream));
+		if (z)
+			HIP_TRY(hipMemcpyAsync(c->d_z, z, px * 4, hipMemcpyHostToDevice, c->stream));
+	}
+	rc = rtx_render_common(c, fr, p, rgb ? c->d_rgb : nullptr, z ? c->d_z : nullptr, c->stream, c->d_tile_list, n_tiles);
 	if (rc)
 		return rc;
 	if (rgb)

@@ -653,7 +653,16 @@ __device__ __forceinline__ void gi_batch(const DScene &S, const DParams &P, uint
 	}
 }
 
-template <bool COUNT>
+/* The tiles of a launch: LIST = false, the arithmetic shard tile_offset + pos * tile_stride of DParams, and no
+ * argument (an empty record); LIST = true, a caller's list (rtx_render_tiles*), read at the chunk position
+ * through a wave-uniform load.  The pointer is a kernel argument of the true instances alone and not a field
+ * of DParams, which k_shadow copies into LDS. */
+template <bool LIST> struct TileList {};
+template <> struct TileList<true> {
+	const uint32_t *__restrict__ p;
+};
+
+template <bool COUNT, bool LIST>
 #ifndef RTX_TRACE_OCC
 #define RTX_TRACE_OCC 6 /* waves per SIMD k_trace is register-capped for (80 VGPRs; with 9 LDS stack entries, 24 waves per CU) */
 #endif
@@ -661,7 +670,8 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 						float *__restrict__ zbuf, DTask *__restrict__ tasks, uint32_t task_cap,
 						float4 *__restrict__ staging, uint32_t staging_cap,
 						float4 *__restrict__ sp_out, uint32_t sp_cap, uint2 *__restrict__ tile_rec,
-						uint32_t tile_begin, uint32_t tile_end, unsigned long long *__restrict__ ctr)
+						uint32_t tile_begin, uint32_t tile_end, unsigned long long *__restrict__ ctr,
+						TileList<LIST> tile_list)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	float *gp_tab = (float *)lds_raw;
@@ -686,7 +696,11 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 		tile = uni(__shfl(tile, 0, WAVE)) + tile_begin;
 		if (tile >= tile_end)
 			break;
-		const uint32_t g = P.tile_offset + tile * P.tile_stride;
+		uint32_t g;
+		if constexpr (LIST)
+			g = uni(tile_list.p[tile]);
+		else
+			g = P.tile_offset + tile * P.tile_stride;
 		const uint32_t tx = g % P.tiles_x, ty = g / P.tiles_x;
 		const uint32_t px = tx * RTX_TILE_W + (lane_id() & 7), py = ty * RTX_TILE_H + (lane_id() >> 3);
 		const bool valid_px = px < F.width && py < F.height;
@@ -900,9 +914,10 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 /* k_accum: one wave per tile adds its shade points' light terms to the     */
 /* tile's pixels in emission order (deterministic, no float atomics)        */
 /* ------------------------------------------------------------------------ */
+template <bool LIST>
 __global__ __launch_bounds__(WAVE) void k_accum(DFrame F, DParams P, const uint2 *__restrict__ tile_rec,
 						 const float4 *__restrict__ contrib, uint32_t tile_begin,
-						 float *__restrict__ rgb)
+						 float *__restrict__ rgb, TileList<LIST> tile_list)
 {
 	const uint32_t t = blockIdx.x;
 	const uint2 rec = tile_rec[t];
@@ -914,7 +929,11 @@ __global__ __launch_bounds__(WAVE) void k_accum(DFrame F, DParams P, const uint2
 			c = contrib[rec.x + base + lane_id()];
 		route_add(acc, valid, valid ? __float_as_uint(c.w) : 0u, mk3(c.x, c.y, c.z));
 	}
-	const uint32_t g = P.tile_offset + (tile_begin + t) * P.tile_stride;
+	uint32_t g;
+	if constexpr (LIST)
+		g = uni(tile_list.p[tile_begin + t]);
+	else
+		g = P.tile_offset + (tile_begin + t) * P.tile_stride;
 	const uint32_t px = (g % P.tiles_x) * RTX_TILE_W + (lane_id() & 7), py = (g / P.tiles_x) * RTX_TILE_H + (lane_id() >> 3);
 	if (px < F.width && py < F.height) {
 		const size_t pix = (size_t)py * F.width + px;
@@ -1177,7 +1196,7 @@ extern "C" size_t rtx_trace_lds_bytes(uint32_t stack_size)
 
 extern "C" hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu)
 {
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_trace<false>, WAVE,
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_trace<false, false>, WAVE,
 							     rtx_trace_lds_bytes(stack_size));
 }
 
@@ -1185,25 +1204,36 @@ extern "C" hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const D
 				       DTask *tasks, uint32_t task_cap, float4 *staging, uint32_t staging_cap,
 				       float4 *sp_out, uint32_t sp_cap, uint2 *tile_rec, uint32_t tile_begin,
 				       uint32_t tile_end, unsigned long long *ctr, uint32_t waves, int count,
-				       hipStream_t stream)
+				       const uint32_t *tile_list, hipStream_t stream)
 {
 	const size_t lds = rtx_trace_lds_bytes(S->stack_size);
-	if (count)
-		hipLaunchKernelGGL(k_trace<true>, dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, task_cap,
-				   staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr);
+#define RTX_TRACE_LAUNCH(C, L, ...) \
+	hipLaunchKernelGGL((k_trace<C, L>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, task_cap, staging, \
+			   staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ })
+	if (tile_list && count)
+		RTX_TRACE_LAUNCH(true, true, tile_list);
+	else if (tile_list)
+		RTX_TRACE_LAUNCH(false, true, tile_list);
+	else if (count)
+		RTX_TRACE_LAUNCH(true, false);
 	else
-		hipLaunchKernelGGL(k_trace<false>, dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,
-				   task_cap, staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr);
+		RTX_TRACE_LAUNCH(false, false);
+#undef RTX_TRACE_LAUNCH
 	return hipGetLastError();
 }
 
 extern "C" hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec,
 				       const float4 *contrib, uint32_t tile_begin, uint32_t ntiles, float *rgb,
-				       hipStream_t stream)
+				       const uint32_t *tile_list, hipStream_t stream)
 {
 	if (!ntiles || !rgb)
 		return hipSuccess;
-	hipLaunchKernelGGL(k_accum, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb);
+	if (tile_list)
+		hipLaunchKernelGGL(k_accum<true>, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb,
+				   TileList<true>{ tile_list });
+	else
+		hipLaunchKernelGGL(k_accum<false>, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb,
+				   TileList<false>{});
 	return hipGetLastError();
 }
 
@@ -1259,5 +1289,5 @@ extern "C" hipError_t rtx_launch_kat(int kind, uint32_t n, const float *in, floa
 extern "C" __attribute__((visibility("hidden"))) hipError_t rtx_load_trace(void)
 {
 	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *)k_accum);
+	return hipFuncGetAttributes(&a, (const void *)k_accum<false>);
 }

@@ -23,6 +23,8 @@
  *   --lens APERTURE FOCUS_DISTANCE   a thin lens of that radius focused at that distance (world units),
  *                pass k from its own lens point; 16 passes unless --passes is given
  *   --target-error E   stop after the first pass (of at least 2) whose error estimate is <= E
+ *   --adaptive   with --target-error E: each 8x8 tile stops receiving passes once its share of the error
+ *                budget is met (rtx_render_adaptive); 16 passes at most unless --passes is given
  *                The multi-pass flags render on one device; --denoise then filters the mean.
  */
 #include <stdio.h>
@@ -58,7 +60,8 @@ static const char *HELPTEXT =
 	"[--passes] (integer)             : DEFAULT = 1       : render the frame this many times (seed + k) and save the mean.\n"
 	"[--aa]                           : DEFAULT = OFF     : anti-aliasing: every pass at its own sub-pixel offset (16 passes unless --passes).\n"
 	"[--lens] (float) (float)         : DEFAULT = OFF     : thin lens: aperture radius and focus distance (16 passes unless --passes).\n"
-	"[--target-error] (float)         : DEFAULT = 0       : stop once the passes' error estimate is at most this (one GPU only).\n";
+	"[--target-error] (float)         : DEFAULT = 0       : stop once the passes' error estimate is at most this (one GPU only).\n"
+	"[--adaptive]                     : DEFAULT = OFF     : with --target-error: a tile stops receiving passes once its share of the error is met.\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -143,8 +146,18 @@ int main(int argc, char **argv)
 		pp.target_error = (float)atof(argv[idx + 1]);
 		multipass = 1;
 	}
+	const int adaptive = argv_find(argc, argv, "--adaptive", 0) != 0;
+	if (adaptive) {
+		if (!(pp.target_error > 0.f)) {
+			LOG("--adaptive needs --target-error E with E above 0.");
+			return 1;
+		}
+		if (!argv_find(argc, argv, "--passes", 1))
+			pp.passes = 16;
+		multipass = 1;
+	}
 	if (multipass && ngpu > 1) {
-		LOG("--passes, --aa, --lens and --target-error render on one GPU, not on %d.", ngpu);
+		LOG("--passes, --aa, --lens, --target-error and --adaptive render on one GPU, not on %d.", ngpu);
 		return 1;
 	}
 
@@ -186,18 +199,30 @@ int main(int argc, char **argv)
 			pp.focus = (float)(focus_distance / (double)desc->camera.focal_length);
 		rtx_ctx *ctx = NULL;
 		rtx_pass_stats ps;
-		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, NULL) ||
-		    rtx_get_pass_stats(ctx, &ps)) {
+		rtx_adaptive_stats as;
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) ||
+		    (adaptive ? rtx_render_adaptive(ctx, &fr, &p, &pp, rgb, z, NULL, NULL) || rtx_get_adaptive_stats(ctx, &as)
+			      : rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, NULL) || rtx_get_pass_stats(ctx, &ps))) {
 			LOG("%s", rtx_last_error());
 			rtx_close(ctx);
 			return 1;
 		}
 		rtx_close(ctx);
-		LOG("Passes: %u of %u run, error %.6g, render %.3f ms, accumulation %.3f ms.", ps.passes_run, pp.passes, ps.error,
-		    ps.render_ms, ps.accum_ms);
-		closest = ps.closest_rays;
-		shadow = ps.shadow_rays;
-		kms = ps.render_ms;
+		if (adaptive) {
+			const double all = (double)as.passes_run * (double)as.tiles;
+			LOG("Adaptive passes: %u of %u run, %llu of %.0f tile passes (%.1f %%), error %.6g, render %.3f ms, fold %.3f ms.",
+			    as.passes_run, pp.passes, (unsigned long long)as.tile_passes, all, all > 0 ? 100.0 * as.tile_passes / all : 0.0,
+			    as.error, as.render_ms, as.fold_ms);
+			closest = as.closest_rays;
+			shadow = as.shadow_rays;
+			kms = as.render_ms;
+		} else {
+			LOG("Passes: %u of %u run, error %.6g, render %.3f ms, accumulation %.3f ms.", ps.passes_run, pp.passes, ps.error,
+			    ps.render_ms, ps.accum_ms);
+			closest = ps.closest_rays;
+			shadow = ps.shadow_rays;
+			kms = ps.render_ms;
+		}
 	} else {
 		rtx_group *grp = NULL;
 		if (rtx_group_open(ngpu, devs, &grp) || rtx_group_upload_scene(grp, desc) ||

@@ -444,6 +444,58 @@ class Renderer:
         _check(self.lib.rtx_get_pass_stats(self._ctx, C.byref(s)))
         return s
 
+    def render_tiles(self, frame, params, tiles, rgb=None, z=None):
+        """rtx_render_tiles on host arrays: the listed 8x8 tiles (row-major indices, strictly increasing) of the
+        frame into rgb / z (zeros when not given); every other pixel keeps its value.  Returns (rgb, z)."""
+        w, h = frame.width, frame.height
+        if rgb is None:
+            rgb = np.zeros((h, w, 3), np.float32)
+        if z is None:
+            z = np.zeros((h, w), np.float32)
+        assert rgb.dtype == np.float32 and rgb.flags.c_contiguous and rgb.size == w * h * 3
+        assert z.dtype == np.float32 and z.flags.c_contiguous and z.size == w * h
+        tiles = np.ascontiguousarray(tiles, dtype=np.uint32).ravel()
+        _check(self.lib.rtx_render_tiles(self._ctx, C.byref(frame), C.byref(params), tiles.ctypes.data if tiles.size else None,
+                                         tiles.size, rgb.ctypes.data, z.ctypes.data))
+        return rgb, z
+
+    def render_tiles_device(self, frame, params, d_tiles, n_tiles, d_rgb, d_z, stream=None):
+        """rtx_render_tiles_device: d_tiles (n_tiles uint32 tile indices), d_rgb and d_z are device pointers (ints);
+        stream: hipStream_t as int or None."""
+        _check(self.lib.rtx_render_tiles_device(self._ctx, C.byref(frame), C.byref(params),
+                                                C.c_void_p(d_tiles) if d_tiles else None, n_tiles,
+                                                C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                                C.c_void_p(stream) if stream else None))
+
+    def render_adaptive(self, frame, params, passes, target_error, min_passes=2, jitter=False, aperture=0.0, focus=1.0):
+        """rtx_render_adaptive on host arrays: multi-pass rendering in which a tile stops receiving passes once its
+        share of the error budget target_error is met, `passes` at the most.  Returns (rgb (h, w, 3) the mean, z (h, w)
+        pass 0's, variance (h, w, 3) of the mean, tile_passes (tiles_y, tiles_x) uint32); adaptive_stats() tells the
+        passes run and the final error."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        tp = np.zeros(((h + 7) // 8, (w + 7) // 8), np.uint32)
+        _check(self.lib.rtx_render_adaptive(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), rgb.ctypes.data,
+                                            z.ctypes.data, var.ctypes.data, tp.ctypes.data))
+        return rgb, z, var, tp
+
+    def render_adaptive_device(self, frame, params, passes, target_error, d_rgb, d_z, d_variance, d_tile_passes, stream=None,
+                               min_passes=2, jitter=False, aperture=0.0, focus=1.0):
+        """rtx_render_adaptive_device: d_rgb / d_z / d_variance / d_tile_passes are device pointers (ints, 16-byte
+        aligned) or None; stream: hipStream_t as int or None."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        _check(self.lib.rtx_render_adaptive_device(self._ctx, C.byref(frame), C.byref(params), C.byref(pp),
+                                                   *[C.c_void_p(d) if d else None for d in (d_rgb, d_z, d_variance, d_tile_passes)],
+                                                   C.c_void_p(stream) if stream else None))
+
+    def adaptive_stats(self):
+        s = abi.AdaptiveStats()
+        _check(self.lib.rtx_get_adaptive_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)

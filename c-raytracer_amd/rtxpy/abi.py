@@ -213,6 +213,11 @@ class PassStats(C.Structure):
                 ("accum_ms", C.c_double), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
 
+class AdaptiveStats(C.Structure):
+    _fields_ = [("passes_run", C.c_uint32), ("tiles", C.c_uint32), ("tile_passes", C.c_uint64), ("error", C.c_double),
+                ("render_ms", C.c_double), ("fold_ms", C.c_double), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
+
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -241,7 +246,9 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_frame_features_device", "rtx_frame_features", "rtx_denoise_params_default", "rtx_denoise_device",
                "rtx_denoise", "rtx_get_denoise_stats",
                "rtx_pass_params_default", "rtx_pass_frame", "rtx_render_passes", "rtx_render_passes_device",
-               "rtx_get_pass_stats"]
+               "rtx_get_pass_stats",
+               "rtx_render_tiles", "rtx_render_tiles_device",
+               "rtx_render_adaptive", "rtx_render_adaptive_device", "rtx_get_adaptive_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -419,6 +426,20 @@ def declare_rtx(lib):
     lib.rtx_render_passes_device.restype = C.c_int
     lib.rtx_get_pass_stats.argtypes = [C.c_void_p, C.POINTER(PassStats)]
     lib.rtx_get_pass_stats.restype = C.c_int
+    lib.rtx_render_tiles.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p]
+    lib.rtx_render_tiles.restype = C.c_int
+    lib.rtx_render_tiles_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_tiles_device.restype = C.c_int
+    lib.rtx_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_adaptive.restype = C.c_int
+    lib.rtx_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams),
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_adaptive_device.restype = C.c_int
+    lib.rtx_get_adaptive_stats.argtypes = [C.c_void_p, C.POINTER(AdaptiveStats)]
+    lib.rtx_get_adaptive_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

@@ -729,6 +729,64 @@ typedef struct rtx_pass_stats {   /* the last rtx_render_passes* of the context 
 int rtx_get_pass_stats(const rtx_ctx *ctx, rtx_pass_stats *out);
 
 /*
+ * Tile-list renders: exactly the tiles the caller names, each bit for bit the tile rtx_render gives for the whole
+ * frame (a pixel's random numbers are keyed on the seed and the pixel, and a tile's pixels do not depend on which
+ * other tiles are rendered with it).  tiles[i] is a row-major index of an 8x8-pixel tile (tile t covers columns
+ * 8 (t % tiles_x) .. and rows 8 (t / tiles_x) .., tiles_x = ceil(W / 8)); the list is strictly increasing and
+ * every index lies below the frame's tile count ceil(W / 8) * ceil(H / 8).  Pixels of tiles not in the list keep
+ * the caller's values (the host form uploads the caller's buffers first, as rtx_render does for a tile shard).
+ * n_tiles == 0 returns RTX_OK and launches nothing.  params->tile_offset / tile_stride must be 0 / 1.
+ * rtx_get_stats afterwards describes this render: its ray counts are those of the listed tiles only.
+ * RTX_ERR_ARG: a null list with n_tiles > 0, n_tiles above the frame's tile count, a list that is not strictly
+ * increasing or holds an index past the last tile; otherwise the errors of rtx_render.
+ */
+int rtx_render_tiles(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const uint32_t *tiles, uint32_t n_tiles,
+		     float *rgb, float *z);
+/* Same with DEVICE buffers, the list (4-byte aligned) included, enqueued on `stream` (NULL = the context's own).
+ * The list is checked by a kernel whose flag word is read back before anything else is launched. */
+int rtx_render_tiles_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const void *d_tiles,
+			    uint32_t n_tiles, void *d_rgb, void *d_z, void *stream);
+
+/*
+ * Adaptive passes: multi-pass rendering as rtx_render_passes, in which an 8x8 tile stops receiving
+ * passes once its share of the frame's error budget is met.  pp is read as by rtx_render_passes (passes is the
+ * most any tile receives), with target_error > 0 required.  With T the number of tiles, n_t the passes tile t has
+ * received, tau = target_error, and after every pass k
+ *   V_t = sum m2 / (n_t (n_t - 1)),  S_t = sum |mean|   over the channels of the tile's pixels with a finite mean,
+ *   V = sum V_t,  A = sum S_t   over ALL tiles, stopped ones included, in tile order,
+ * tile t receives pass k+1 iff k+1 < min_passes, or it received pass k and V_t T > tau^2 A^2 (in double; a NaN
+ * compares false, so the tile stops).  A stopped tile never restarts: the passes folded into tile t are always
+ * 0 .. n_t - 1, each the tile as rtx_render_tiles renders it for rtx_pass_frame(frame, pp, k) and seed + k.  The
+ * run ends after pass k when no tile is left or k + 1 == passes.
+ *   rgb, variance   as rtx_render_passes, per pixel with its tile's n_t (variance 0 where n_t = 1)
+ *   z               pass 0's
+ *   tile_passes[T]  n_t, row-major tiles
+ * HOST buffers; each may be NULL.  Every sum has a fixed order and no atomics: two runs give the same bits and
+ * the same counts.
+ * The error reported is sqrt(V) / A after the last pass (0 if A == 0), rtx_render_passes's E.  When every tile
+ * has stopped on the rule, sum V_t <= tau^2 times the mean of A^2 at the tiles' stops, so E is ABOUT tau; it is
+ * NOT guaranteed to be <= tau, because A goes on moving after a tile has stopped.  Read the final error from
+ * rtx_get_adaptive_stats.
+ * RTX_ERR_ARG: target_error not above 0, and every error of rtx_render_passes, raised before anything is
+ * launched.  rtx_get_stats afterwards describes the last pass's tile-list render.  Device groups have no such entry.
+ */
+int rtx_render_adaptive(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			float *rgb, float *z, float *variance, uint32_t *tile_passes);
+/* Same into DEVICE buffers (16-byte aligned, each may be NULL), enqueued on `stream` (NULL = the context's
+ * own); synchronises the stream. */
+int rtx_render_adaptive_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			       void *d_rgb, void *d_z, void *d_variance, void *d_tile_passes, void *stream);
+typedef struct rtx_adaptive_stats {   /* the last rtx_render_adaptive* of the context */
+	uint32_t passes_run, tiles;      /* R = max n_t, and T */
+	uint64_t tile_passes;            /* sum of n_t over the tiles (R T for a run that stopped no tile early) */
+	double error;                    /* sqrt(V) / A after the last pass */
+	double render_ms;                /* sum of the passes' rtx_stats.kernel_ms */
+	double fold_ms;                  /* the fold / select / output kernels, HIP events */
+	uint64_t closest_rays, shadow_rays;   /* summed over the passes */
+} rtx_adaptive_stats;
+int rtx_get_adaptive_stats(const rtx_ctx *ctx, rtx_adaptive_stats *out);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
