@@ -38,33 +38,9 @@
 #include <thread>
 #include <vector>
 
+#include "rtx_group_internal.h"
 #include "rtx_internal.h"
 #include "rtx_tiles.h"
-
-#define NCCL_TRY(expr)                                                                                  \
-	do {                                                                                            \
-		ncclResult_t r_ = (expr);                                                               \
-		if (r_ != ncclSuccess)                                                                  \
-			return fail(RTX_ERR_HIP, "%s failed: %s", #expr, ncclGetErrorString(r_));       \
-	} while (0)
-
-struct rtx_group {
-	int n = 0;
-	bool loopback = false;         /* rtx_group_open_loopback: every context on one device */
-	bool rccl_self = false;        /* rtx_group_open_rccl_self: shard 0 sent to itself over RCCL */
-	std::vector<uint32_t> peer;    /* peer access between device r and device 0 enabled */
-	std::vector<rtx_ctx *> ctx;
-	std::vector<ncclComm_t> comm;  /* n > 1 or rccl_self: one per device, rank r = ctx[r] */
-	std::vector<float4 *> d_buf;   /* r > 0 (rccl_self: r = 0): shard r's packed records on device r */
-	std::vector<float4 *> d_recv;  /* the same shards' records received on device 0 */
-	std::vector<size_t> buf_cap;   /* capacity of d_buf[r] in records */
-	std::vector<size_t> recv_cap;  /* capacity of d_recv[r] in records */
-	rtx_stats stats{};
-	rtx_point_stats pstats{};
-	rtx_dark_stats dstats{};
-	rtx_order_stats ostats{};
-	rtx_premask_stats mstats{};
-};
 
 extern "C" void rtx_group_close(rtx_group *g)
 {
@@ -76,11 +52,20 @@ extern "C" void rtx_group_close(rtx_group *g)
 		(void)hipSetDevice(g->ctx[r]->device);
 		if (r < (int)g->d_buf.size())
 			dfree(g->d_buf[r]);
+		if (r < (int)g->ps_stat.size())
+			dfree(g->ps_stat[r].p);
+		if (r < (int)g->ps_rec.size())
+			dfree(g->ps_rec[r].p);
 	}
 	if (!g->ctx.empty() && g->ctx[0]) {
 		(void)hipSetDevice(g->ctx[0]->device);
 		for (auto &p : g->d_recv)
 			dfree(p);
+		for (auto &b : g->ps_stat_recv)
+			dfree(b.p);
+		for (auto &b : g->ps_rec_recv)
+			dfree(b.p);
+		dfree(g->ps_list_recv.p);
 	}
 	for (ncclComm_t c : g->comm)
 		if (c)

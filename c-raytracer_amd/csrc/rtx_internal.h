@@ -2,7 +2,7 @@
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
  * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
- * rtx_passes.cpp (multi-pass rendering, adaptive passes) and rtx_group.cpp (multi-device).  The device context, its scratch buffers' owner type, a
+ * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
@@ -331,6 +331,9 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 RTX_HIDDEN void rtx_free_scene(rtx_ctx *c);
 /* rtx_query.cpp: n checked rays on device buffers into c->ray_stats (the feature buffers' query too) */
 RTX_HIDDEN int rtx_rays_common(rtx_ctx *c, uint32_t n, const void *d_rays, void *d_hits, uint32_t flags, hipStream_t stream);
+
+/* rtx_passes.cpp: what the multi-pass (adaptive: and the adaptive) entries refuse about non-null arguments */
+RTX_HIDDEN int rtx_passes_args_check(const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive);
 
 /* Steps that more than one entry point takes.  They return the HIP error and each caller reports it
  * with its own code and text. */

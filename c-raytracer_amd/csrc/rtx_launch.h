@@ -102,6 +102,17 @@ hipError_t rtx_launch_tile_pack(const float *rgb, const float *z, uint32_t w, ui
 				float4 *out, hipStream_t stream);
 hipError_t rtx_launch_tile_unpack(const float4 *in, uint32_t w, uint32_t h, uint32_t off, uint32_t stride, float *rgb,
 				  float *z, hipStream_t stream);
+/* ... and a group's multi-pass renders: tile statistics, a list's shard, pass records */
+RTX_HIDDEN hipError_t rtx_launch_stat_pack(const double *vs, const uint32_t *count, uint32_t total, uint32_t off, uint32_t stride,
+					   uint32_t ntiles, void *out, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_stat_scatter(const void *in, uint32_t total, uint32_t off, uint32_t stride, uint32_t ntiles,
+					      double *vs, uint32_t *count, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_list_shard(const uint32_t *in, uint32_t n_in, uint32_t total, uint32_t off, uint32_t stride,
+					    uint32_t *out, uint32_t *n_out, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_pass_pack(const float *rgb, const float *z, const float *var, uint32_t w, uint32_t h,
+					   uint32_t off, uint32_t stride, float4 *out, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_pass_unpack(const float4 *in, uint32_t w, uint32_t h, uint32_t off, uint32_t stride, float *rgb,
+					     float *z, float *var, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_gather(void);
 
 /* rtx_denoise.hip */

@@ -106,20 +106,34 @@ extern "C" int rtx_pass_frame(const rtx_frame *fr, const rtx_pass_params *pp, ui
 	return RTX_OK;
 }
 
-/* everything rtx_render_passes* refuses before it launches anything */
-static int passes_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp)
+/* what rtx_render_passes* (and, adaptive, rtx_render_adaptive*) refuse about a frame, its parameters and its pass
+ * parameters, none of them null; the device group's entries share it (rtx_group_passes.cpp) */
+int rtx_passes_args_check(const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive)
 {
-	if (!c || !fr || !p || !pp)
-		return fail(RTX_ERR_ARG, "null argument");
-	if (!c->have_scene)
-		return fail(RTX_ERR_STATE, "rtx_render_passes before rtx_upload_scene");
 	if (!fr->width || !fr->height)
 		return fail(RTX_ERR_ARG, "empty frame %ux%u", fr->width, fr->height);
 	if (p->tile_offset != 0 || p->tile_stride != 1)
 		return fail(RTX_ERR_ARG, "rtx_render_passes renders whole frames: tile sharding %u/%u is not 0/1", p->tile_offset,
 			    p->tile_stride);
 	rtx_frame f0;
-	return rtx_pass_frame(fr, pp, 0, &f0);
+	int rc = rtx_pass_frame(fr, pp, 0, &f0);
+	if (rc || !adaptive)
+		return rc;
+	if (!(pp->target_error > 0.f))
+		return fail(RTX_ERR_ARG, "adaptive passes need a target error above 0");
+	if (rtx_tiles_total(fr->width, fr->height) > (1ull << 26))
+		return fail(RTX_ERR_ARG, "frame %ux%u has more than 2^26 tiles", fr->width, fr->height);
+	return RTX_OK;
+}
+
+/* everything rtx_render_passes* refuses before it launches anything */
+static int passes_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive = false)
+{
+	if (!c || !fr || !p || !pp)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (!c->have_scene)
+		return fail(RTX_ERR_STATE, "rtx_render_passes before rtx_upload_scene");
+	return rtx_passes_args_check(fr, p, pp, adaptive);
 }
 
 /* checked arguments, device outputs (each may be null) */
@@ -212,14 +226,7 @@ extern "C" int rtx_render_passes(rtx_ctx *c, const rtx_frame *fr, const rtx_para
 /* everything rtx_render_adaptive* refuses before it launches anything */
 static int adaptive_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp)
 {
-	int rc = passes_check(c, fr, p, pp);
-	if (rc)
-		return rc;
-	if (!(pp->target_error > 0.f))
-		return fail(RTX_ERR_ARG, "adaptive passes need a target error above 0");
-	if (rtx_tiles_total(fr->width, fr->height) > (1ull << 26))
-		return fail(RTX_ERR_ARG, "frame %ux%u has more than 2^26 tiles", fr->width, fr->height);
-	return RTX_OK;
+	return passes_check(c, fr, p, pp, true);
 }
 
 /* checked arguments, device outputs (each may be null) */

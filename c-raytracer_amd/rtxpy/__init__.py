@@ -619,6 +619,45 @@ class Group:
         _check(self.lib.rtx_group_device_order_stats(self._g, r, C.byref(o)))
         return _with_point_stats(s, p, d, m, o)
 
+    def render_passes(self, frame, params, passes, jitter=False, aperture=0.0, focus=1.0, target_error=0.0, min_passes=2):
+        """rtx_group_render_passes on host arrays, as Renderer.render_passes: (rgb, z, variance); pass_stats() tells how
+        many passes ran, exchange_stats() what travelled between the members."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        _check(self.lib.rtx_group_render_passes(self._g, C.byref(frame), C.byref(params), C.byref(pp), rgb.ctypes.data,
+                                                z.ctypes.data, var.ctypes.data))
+        return rgb, z, var
+
+    def pass_stats(self):
+        s = abi.PassStats()
+        _check(self.lib.rtx_group_get_pass_stats(self._g, C.byref(s)))
+        return s
+
+    def render_adaptive(self, frame, params, passes, target_error, min_passes=2, jitter=False, aperture=0.0, focus=1.0):
+        """rtx_group_render_adaptive on host arrays, as Renderer.render_adaptive: (rgb, z, variance, tile_passes), the
+        single context's bits for any number of members."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        tp = np.zeros(((h + 7) // 8, (w + 7) // 8), np.uint32)
+        _check(self.lib.rtx_group_render_adaptive(self._g, C.byref(frame), C.byref(params), C.byref(pp), rgb.ctypes.data,
+                                                  z.ctypes.data, var.ctypes.data, tp.ctypes.data))
+        return rgb, z, var, tp
+
+    def adaptive_stats(self):
+        s = abi.AdaptiveStats()
+        _check(self.lib.rtx_group_get_adaptive_stats(self._g, C.byref(s)))
+        return s
+
+    def exchange_stats(self):
+        """rtx_group_get_exchange_stats: exchanges, bytes, exchange_ms and gather_ms of the last multi-pass render"""
+        s = abi.GroupExchangeStats()
+        _check(self.lib.rtx_group_get_exchange_stats(self._g, C.byref(s)))
+        return s
+
     def member(self, r):
         """what the runtime reports about member r (rtx_group_member_info): its device, its RCCL
         communicator's count / rank / device, peer access to and from member 0, PCI bus id"""
@@ -658,3 +697,27 @@ def tile_unpack(records, rgb, z, offset, stride):
     assert rgb.dtype == np.float32 and rgb.flags.c_contiguous and z.dtype == np.float32 and z.flags.c_contiguous
     h, w = z.shape
     _check(rtx_lib().rtx_tile_unpack_host(records.ctypes.data, w, h, offset, stride, rgb.ctypes.data, z.ctypes.data))
+
+
+def pass_pack(rgb, z, variance, offset, stride):
+    """rtx_pass_pack_host: the shard's (N, 8) float32 pass records {mean r, g, b, z, var r, g, b, 0}."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    variance = np.ascontiguousarray(variance, dtype=np.float32)
+    h, w = z.shape
+    lib = rtx_lib()
+    n = lib.rtx_tile_pack_count(w, h, offset, stride)
+    out = np.zeros((n, 8), np.float32)
+    _check(lib.rtx_pass_pack_host(rgb.ctypes.data, z.ctypes.data, variance.ctypes.data, w, h, offset, stride, out.ctypes.data))
+    return out
+
+
+def pass_unpack(records, shape, offset, stride, rgb=None, z=None, variance=None):
+    """rtx_pass_unpack_host: writes the shard's pixels of records into rgb / z / variance in place, each float32 of a
+    frame of shape (h, w) or None."""
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    h, w = shape
+    for a, words in ((rgb, 3), (z, 1), (variance, 3)):
+        assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous and a.size == w * h * words)
+    _check(rtx_lib().rtx_pass_unpack_host(records.ctypes.data, w, h, offset, stride, *[a.ctypes.data if a is not None else None
+                                                                                          for a in (rgb, z, variance)]))

@@ -218,6 +218,12 @@ class AdaptiveStats(C.Structure):
                 ("render_ms", C.c_double), ("fold_ms", C.c_double), ("closest_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
 
+class GroupExchangeStats(C.Structure):
+    """rtx_group_exchange_stats: what the last rtx_group_render_passes / rtx_group_render_adaptive moved between members"""
+    _fields_ = [("exchanges", C.c_uint32), ("pad_", C.c_uint32), ("bytes", C.c_uint64), ("exchange_ms", C.c_double),
+                ("gather_ms", C.c_double)]
+
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -248,7 +254,10 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_pass_params_default", "rtx_pass_frame", "rtx_render_passes", "rtx_render_passes_device",
                "rtx_get_pass_stats",
                "rtx_render_tiles", "rtx_render_tiles_device",
-               "rtx_render_adaptive", "rtx_render_adaptive_device", "rtx_get_adaptive_stats"]
+               "rtx_render_adaptive", "rtx_render_adaptive_device", "rtx_get_adaptive_stats",
+               "rtx_group_render_passes", "rtx_group_get_pass_stats", "rtx_group_render_adaptive",
+               "rtx_group_get_adaptive_stats", "rtx_group_get_exchange_stats",
+               "rtx_pass_pack_host", "rtx_pass_unpack_host", "rtx_pass_pack_device", "rtx_pass_unpack_device"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -440,6 +449,30 @@ def declare_rtx(lib):
     lib.rtx_render_adaptive_device.restype = C.c_int
     lib.rtx_get_adaptive_stats.argtypes = [C.c_void_p, C.POINTER(AdaptiveStats)]
     lib.rtx_get_adaptive_stats.restype = C.c_int
+    lib.rtx_group_render_passes.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+    lib.rtx_group_render_passes.restype = C.c_int
+    lib.rtx_group_get_pass_stats.argtypes = [C.c_void_p, C.POINTER(PassStats)]
+    lib.rtx_group_get_pass_stats.restype = C.c_int
+    lib.rtx_group_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_group_render_adaptive.restype = C.c_int
+    lib.rtx_group_get_adaptive_stats.argtypes = [C.c_void_p, C.POINTER(AdaptiveStats)]
+    lib.rtx_group_get_adaptive_stats.restype = C.c_int
+    lib.rtx_group_get_exchange_stats.argtypes = [C.c_void_p, C.POINTER(GroupExchangeStats)]
+    lib.rtx_group_get_exchange_stats.restype = C.c_int
+    lib.rtx_pass_pack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_void_p]
+    lib.rtx_pass_pack_host.restype = C.c_int
+    lib.rtx_pass_unpack_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    lib.rtx_pass_unpack_host.restype = C.c_int
+    lib.rtx_pass_pack_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.rtx_pass_pack_device.restype = C.c_int
+    lib.rtx_pass_unpack_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_pass_unpack_device.restype = C.c_int
 
 
 def declare_oracle(lib):

@@ -711,7 +711,7 @@ int rtx_pass_frame(const rtx_frame *frame, const rtx_pass_params *pp, uint32_t k
  * in index order, no atomics): two runs stop after the same pass and return the same bits.
  * params->tile_offset / tile_stride must be 0 / 1.  Errors as rtx_render (RTX_ERR_STATE before an upload),
  * and every rtx_pass_frame error, raised before anything is launched.  rtx_get_stats afterwards describes the
- * last pass.  Device groups have no such entry.
+ * last pass.  Device groups: rtx_group_render_passes.
  */
 int rtx_render_passes(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
 		      float *rgb, float *z, float *variance);
@@ -768,7 +768,8 @@ int rtx_render_tiles_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_para
  * NOT guaranteed to be <= tau, because A goes on moving after a tile has stopped.  Read the final error from
  * rtx_get_adaptive_stats.
  * RTX_ERR_ARG: target_error not above 0, and every error of rtx_render_passes, raised before anything is
- * launched.  rtx_get_stats afterwards describes the last pass's tile-list render.  Device groups have no such entry.
+ * launched.  rtx_get_stats afterwards describes the last pass's tile-list render.  Device groups:
+ * rtx_group_render_adaptive.
  */
 int rtx_render_adaptive(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
 			float *rgb, float *z, float *variance, uint32_t *tile_passes);
@@ -785,6 +786,63 @@ typedef struct rtx_adaptive_stats {   /* the last rtx_render_adaptive* of the co
 	uint64_t closest_rays, shadow_rays;   /* summed over the passes */
 } rtx_adaptive_stats;
 int rtx_get_adaptive_stats(const rtx_ctx *ctx, rtx_adaptive_stats *out);
+
+/*
+ * Multi-pass and adaptive rendering on a device group.  Member r owns the tiles t = r (mod n)
+ * and keeps their Welford state, n_t, V_t and S_t at the GLOBAL tile index, in the arrays a single context holds
+ * (48 B per pixel on every member; it never touches the other members' slices).  The fold, the selection and the
+ * output are rtx_render_adaptive's own kernels, so every result below is rtx_render_adaptive's to the bit for any
+ * number of members.  Host buffers only; every output may be NULL.  The argument errors are those of
+ * rtx_render_passes / rtx_render_adaptive (params->tile_offset / tile_stride 0 / 1 included) and a frame of more
+ * than 2^25 tiles, all raised before anything is launched; a null group is RTX_ERR_ARG, a call before
+ * rtx_group_upload_scene RTX_ERR_STATE.  A refused call leaves the statistics of the last successful one as they were.
+ *
+ * rtx_group_render_adaptive, per pass k: every member, on its own host thread, list-renders its active tiles
+ * (z on pass 0), folds them and packs {V_t, S_t, n_t} of ALL its tiles (24 B each); the records travel to member 0,
+ * which scatters them into its global arrays and runs the selection over all T tiles: V, A, the next list and its
+ * length are a single context's.  The list travels to every member, which keeps its own tiles in order.  A member
+ * with no active tile launches nothing and still takes part in every exchange.  After the last pass every member
+ * forms its pixels' mean and variance and packs 32-byte records {mean r, g, b, z, var r, g, b, 0} (rtx_pass_pack_*),
+ * which one gather brings to member 0.  tile_passes is member 0's n_t array.  Records and lists move as bits.
+ *
+ * rtx_group_render_passes: member r renders its tile shard every pass and folds it with the same per-tile kernel;
+ * the tile statistics travel only after the passes the stopping rule looks at and after the last.  rgb, z and
+ * variance are rtx_render_adaptive's with min_passes == passes, to the bit.  The error is sqrt(V) / A with V and A
+ * summed over the tiles in the selection's order, the error rtx_render_adaptive reports: it does not depend on n,
+ * and differs from rtx_render_passes's block-strided sum by double rounding only (so a target_error within that
+ * rounding of a pass's error may stop the two a pass apart).
+ */
+int rtx_group_render_passes(rtx_group *g, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			    float *rgb, float *z, float *variance);
+/* ray counts summed over members and passes; render_ms the sum over passes of the slowest member's kernel_ms;
+ * accum_ms the sum over passes of the slowest member's fold, plus member 0's selection and output kernels */
+int rtx_group_get_pass_stats(const rtx_group *g, rtx_pass_stats *out);
+int rtx_group_render_adaptive(rtx_group *g, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			      float *rgb, float *z, float *variance, uint32_t *tile_passes);
+/* likewise, fold_ms as accum_ms above */
+int rtx_group_get_adaptive_stats(const rtx_group *g, rtx_adaptive_stats *out);
+typedef struct rtx_group_exchange_stats { /* the last rtx_group_render_passes / rtx_group_render_adaptive */
+	uint32_t exchanges;      /* passes after which statistics (and, adaptive, the next list) travelled; 0 when nothing
+	                          * travels (one member without RCCL) */
+	uint32_t pad_;
+	uint64_t bytes;          /* bytes moved between members: every exchange and the final gather */
+	double exchange_ms;      /* host wall time of the per-pass exchanges (moves, scatter, list filter, count reads) */
+	double gather_ms;        /* host wall time of the final record gather and its unpack */
+} rtx_group_exchange_stats;
+int rtx_group_get_exchange_stats(const rtx_group *g, rtx_group_exchange_stats *out);
+
+/* The pass records of the gather above: shard `offset` of `stride` of a W x H frame packs to rtx_tile_pack_count()
+ * records of 8 floats {mean r, g, b, z, var r, g, b, 0}, 64 per tile in the tile records' pixel order, pixels
+ * outside the frame as zeros; every value keeps its bits.  Host reference and device versions; the outputs of an
+ * unpack may be NULL. */
+int rtx_pass_pack_host(const float *rgb, const float *z, const float *variance, uint32_t width, uint32_t height,
+		       uint32_t offset, uint32_t stride, float *out);
+int rtx_pass_unpack_host(const float *in, uint32_t width, uint32_t height, uint32_t offset, uint32_t stride, float *rgb,
+			 float *z, float *variance);
+int rtx_pass_pack_device(rtx_ctx *ctx, const void *d_rgb, const void *d_z, const void *d_variance, uint32_t width,
+			 uint32_t height, uint32_t offset, uint32_t stride, void *d_out, void *stream);
+int rtx_pass_unpack_device(rtx_ctx *ctx, const void *d_in, uint32_t width, uint32_t height, uint32_t offset,
+			   uint32_t stride, void *d_rgb, void *d_z, void *d_variance, void *stream);
 
 /*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
