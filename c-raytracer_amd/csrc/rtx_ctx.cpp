@@ -226,6 +226,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow sample order %lld is not 0 or 1", (long long)value);
 		c->opt_order = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_SPEC:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow specular shortcut %lld is not 0 or 1", (long long)value);
+		c->opt_spec = (int)value;
+		return RTX_OK;
 	case RTX_OPT_SHADOW_PREMASK:
 		if (value < 0 || value > 1)
 			return fail(RTX_ERR_ARG, "shadow pre-mask %lld is not 0 or 1", (long long)value);

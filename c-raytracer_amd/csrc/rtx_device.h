@@ -274,6 +274,8 @@ typedef struct DScene {
 	                        * light points across the cone (rtx_shadow.hip order_begin) */
 	uint32_t *ordbuf;      /* ... the waves' order / result slices, RTX_ORD_WORDS words per grid wave */
 	uint32_t ordbuf_waves; /* grid waves the buffer was sized for (0: none) */
+	uint32_t spec;         /* RTX_OPT_SHADOW_SPEC: a wave-uniform point of shininess 0 skips the specular factor of its
+	                        * samples (rtx_shadow.hip shade_terms_s0) */
 } DScene;
 #define RTX_ORD_CAP 1024u                /* most samples of one emitter a point orders */
 #define RTX_ORD_BUCKETS 16u              /* buckets of the key */

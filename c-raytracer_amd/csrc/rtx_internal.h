@@ -240,6 +240,7 @@ struct rtx_ctx : CtxHandles {
 	int opt_cull = 1;         /* RTX_OPT_SHADOW_CULL: 0 off, 1 wave-uniform packets, 2 lane slots too */
 	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	int opt_dark = 1;         /* RTX_OPT_SHADOW_DARK: light samples that add nothing skip their shadow query */
+	int opt_spec = 1;         /* RTX_OPT_SHADOW_SPEC: a shininess-0 point's samples skip the specular factor */
 	int opt_order = 1;        /* RTX_OPT_SHADOW_ORDER: a walking point's light samples walked in key order */
 	int opt_premask = 1;      /* RTX_OPT_SHADOW_PREMASK: the per-point masks formed before k_shadow, one point per lane */
 	uint32_t mem_share = 1;  /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point

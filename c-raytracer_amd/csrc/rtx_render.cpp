@@ -190,6 +190,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		Ssh.cull_slots = c->opt_cull == 2 ? 1u : 0u;
 		Ssh.point = (c->opt_cull && c->opt_point) ? 1u : 0u; /* RTX_OPT_SHADOW_POINT */
 		Ssh.dark = (c->opt_cull && c->opt_dark) ? 1u : 0u;   /* RTX_OPT_SHADOW_DARK */
+		Ssh.spec = c->opt_spec ? 1u : 0u;                    /* RTX_OPT_SHADOW_SPEC */
 		/* RTX_OPT_SHADOW_ORDER: wave-uniform packets that walk a tree, the waves' slices for the largest grid */
 		Ssh.order = 0u;
 		Ssh.ordbuf = nullptr;

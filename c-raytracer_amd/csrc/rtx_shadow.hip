@@ -841,6 +841,7 @@ const DW8 *w8;        /* 8-wide compressed BVH (WALK_W8 instances; qo / qs / qsi
 	uint32_t point;       /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	const uint32_t *pm;   /* the points' masks formed before the kernel (k_point_masks), by record index; null:
 	                       * k_shadow forms them itself (point_masks) */
+	uint32_t spec;        /* RTX_OPT_SHADOW_SPEC: a wave-uniform point of shininess 0 takes shade_terms_s0 / dark_terms_s0 */
 };
 
 __device__ __forceinline__ void reread_barrier() { asm volatile("" ::: "memory"); }
@@ -980,6 +981,36 @@ __device__ __forceinline__ bool dark_terms(int32_t att, int32_t refl, f3 n, f3 d
 	return dk && (pw == 0.f || (zero3(ks3) && fin1(pw)));
 }
 
+/* The two for a point of shininess +-0 (RTX_OPT_SHADOW_SPEC).  sh_pow (and powf) give 1 for y == 0
+ * whatever x is, NaN included, so pw = fmaxf(0, 1) = 1 and shade_pw, the reflection vector, its dot
+ * product, the logarithm and the sign rule, need not run.  spec = (ks li) * 1 is ks li bit for bit
+ * (a product is never a signalling NaN, and denormals are kept); pd, li attf, diff and the final sum
+ * are shade_terms' operations in its order.  In dark_terms pw == 0 is false and fin1(pw) true, and
+ * its early return only skips pw.  The callers branch here on the point's shininess where it is
+ * wave-uniform (shin_zero of a scalar), so the lanes run none of what is left out; per-lane points
+ * keep the generic forms.  (KAT: RTX_KAT_SPEC0) */
+__device__ __forceinline__ bool shin_zero(float shin) { return (__float_as_uint(shin) << 1) == 0u; } /* shin == 0.f, on the bits */
+__device__ __forceinline__ f3 shade_terms_s0(int32_t att, f3 n, f3 kd, f3 ks3, f3 ldir, f3 li, float attf)
+{
+	float a;
+	const float pd = shade_pd(n, ldir, a);
+	if (att != RTX_ATT_NONE)
+		li = mul3s(li, attf);
+	const f3 diff = mul3s(mul3v(kd, li), pd);
+	const f3 spec = mul3v(ks3, li);
+	return add3(diff, spec);
+}
+__device__ __forceinline__ bool dark_terms_s0(int32_t att, f3 n, f3 kd, f3 ks3, f3 ldir, f3 li, float attf, bool act)
+{
+	float a;
+	const float pd = shade_pd(n, ldir, a);
+	if (att != RTX_ATT_NONE)
+		li = mul3s(li, attf);
+	const bool fin = fin1(attf) && fin3(mul3v(kd, li)) && fin3(mul3v(ks3, li));
+	const bool dk = act && fin && (pd == 0.f || (zero3(kd) && fin1(pd)));
+	return dk && zero3(ks3);
+}
+
 /* the shading inputs of the shade point `rec`: normal, view direction, diffuse colour and its
  * material's ks / shininess (UNI: a wave-uniform record and its material through scalar reads) */
 template <bool UNI>
@@ -1007,6 +1038,8 @@ __device__ __forceinline__ f3 shade_light(const KShadow &ks, const float4 *rec, 
 	f3 n, dir, kd, ks3;
 	float shin;
 	point_shading<UNI>(ks, rec, n, dir, kd, ks3, shin);
+	if (UNI && shin_zero(shin) && uni(ks.spec)) /* a wave-uniform branch: shin is a scalar here */
+		return shade_terms_s0((int32_t)uni((uint32_t)ks.attenuation), n, kd, ks3, ldir, li, attf);
 	return shade_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, kd, ks3, shin, ldir, li,
 			   attf);
 }
@@ -1018,6 +1051,8 @@ __device__ __forceinline__ bool sample_dark(const KShadow &ks, const float4 *rec
 	f3 n, dir, kd, ks3;
 	float shin;
 	point_shading<UNI>(ks, rec, n, dir, kd, ks3, shin);
+	if (UNI && shin_zero(shin) && uni(ks.spec))
+		return dark_terms_s0((int32_t)uni((uint32_t)ks.attenuation), n, kd, ks3, ldir, li, attf, act);
 	return dark_terms((int32_t)uni((uint32_t)ks.attenuation), (int32_t)uni((uint32_t)ks.reflection), n, dir, kd, ks3, shin, ldir, li,
 			  attf, act);
 }
@@ -1490,6 +1525,35 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	return contribution;
 }
 
+/* clear_run's packets of emitter E, whose samples are [start, end), from `base` up to the first that
+ * straddles the next emitter or nl; S0: the point's shininess is 0 (shade_terms_s0).  Returns the rays. */
+template <bool COUNT, bool S0>
+__device__ __forceinline__ uint32_t clear_packets(const DEmitter &E, uint64_t mix, int32_t rng, int32_t att, int32_t refl, float att_offset,
+						  f3 p, f3 n, f3 dir, f3 kd, f3 ks3, float shin, uint32_t nl, uint32_t start, uint32_t end,
+						  uint32_t &base, f3 &acc)
+{
+	uint32_t rays = 0;
+	for (; base < nl && min(base + WAVE, nl) <= end; base += WAVE) {
+		const uint32_t idx = base + lane_id(), j = idx - start;
+		const bool act = idx < nl;
+		float u1 = 0.5f, u2 = 0.5f;
+		if (rng != RTX_RNG_CONST)
+			rtx_draw2_mixed(mix, j, &u1, &u2);
+		f3 ldir, li;
+		float ldist, dsq;
+		sample_ray(rng, E, j, u1, u2, p, ldir, ldist, dsq, li);
+		const float attf = sample_att_of(att, att_offset, ldist, dsq);
+		f3 contribution = mk3(0.f, 0.f, 0.f);
+		if (act)
+			contribution = S0 ? shade_terms_s0(att, n, kd, ks3, ldir, li, attf) :
+					    shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf);
+		acc = add3(acc, contribution);
+		if (COUNT)
+			rays += popc64(ballot(act));
+	}
+	return rays;
+}
+
 /* The packets of an all-clear shade point `rec` (point_masks: for every emitter it samples, the
  * tree part, the planes and the listed records are clear), from sample `base` on: every sample is
  * unblocked and its intensity untouched, so a packet inside one emitter's samples is light_sample
@@ -1511,8 +1575,11 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
 	const auto &mat = cptr(unip(ks.mats))[__float_as_uint(q3.w)];
 	const f3 ks3 = mk3(mat.ks[0], mat.ks[1], mat.ks[2]);
 	const float shin = mat.shininess;
+	/* RTX_OPT_SHADOW_SPEC: a shininess-0 point's packets run shade_terms_s0, which reads no reflection model:
+	 * refl = -1 says so (one scalar fewer across the loops than a flag of its own, which cost the walking
+	 * instances SGPR spills); else RTX_BLINN or, as shade_pw reads every other value, RTX_PHONG */
 	const int32_t rng = (int32_t)uni((uint32_t)ks.rng), att = (int32_t)uni((uint32_t)ks.attenuation),
-		      refl = (int32_t)uni((uint32_t)ks.reflection);
+		      refl = (shin_zero(shin) && uni(ks.spec)) ? -1 : (int32_t)uni((uint32_t)ks.reflection) == RTX_BLINN ? RTX_BLINN : RTX_PHONG;
 	const float att_offset = __uint_as_float(uni(__float_as_uint(ks.att_offset)));
 	const DEmitter *emitters = unip(ks.emitters);
 	const auto *EM = cptr(emitters);
@@ -1533,24 +1600,9 @@ __device__ __forceinline__ uint32_t clear_run(const KShadow &ks, const float4 *r
 			break;
 		const DEmitter E = emitter_uni(emitters + cur);
 		const uint64_t mix = rtx_draw_mix(key, cur);
-		uint32_t rays = 0;
-		for (; base < nl && min(base + WAVE, nl) <= end; base += WAVE) {
-			const uint32_t idx = base + lane_id(), j = idx - start;
-			const bool act = idx < nl;
-			float u1 = 0.5f, u2 = 0.5f;
-			if (rng != RTX_RNG_CONST)
-				rtx_draw2_mixed(mix, j, &u1, &u2);
-			f3 ldir, li;
-			float ldist, dsq;
-			sample_ray(rng, E, j, u1, u2, p, ldir, ldist, dsq, li);
-			const float attf = sample_att_of(att, att_offset, ldist, dsq);
-			f3 contribution = mk3(0.f, 0.f, 0.f);
-			if (act)
-				contribution = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf);
-			acc = add3(acc, contribution);
-			if (COUNT)
-				rays += popc64(ballot(act));
-		}
+		/* the point's shininess picks the loop, once: the one of a shininess-0 point holds no shade_pw */
+		const uint32_t rays = refl < 0 ? clear_packets<COUNT, true>(E, mix, rng, att, refl, att_offset, p, n, dir, kd, ks3, shin, nl, start, end, base, acc) :
+					   clear_packets<COUNT, false>(E, mix, rng, att, refl, att_offset, p, n, dir, kd, ks3, shin, nl, start, end, base, acc);
 		if (COUNT) {
 			if (WALK == WALK_W8 && ((uni(cmask[cur >> 5]) >> (cur & 31u)) & 1u))
 				sc.clear += rays;
@@ -2341,6 +2393,25 @@ __global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in,
 		y[5] = t1.y;
 		y[6] = t1.z;
 	} break;
+	case RTX_KAT_SPEC0: {
+		/* RTX_KAT_DARK's record through the shininess-0 forms (its shin is not read): what
+		 * dark_terms / shade_terms give for the same record with shin = +-0, bit for bit */
+		const f3 n = ld3(x), kd = ld3(x + 6), ks3 = ld3(x + 9), ldir = ld3(x + 13), li = ld3(x + 17), kt = ld3(x + 23);
+		const float ldist = x[16];
+		const int32_t att = (int32_t)x[20];
+		const float attf = sample_att_of(att, x[21], ldist, ldist * ldist);
+		const bool ok = fin3(li) && fabsf(kt.x) <= 1.f && fabsf(kt.y) <= 1.f && fabsf(kt.z) <= 1.f; /* scene_dark_ok */
+		const bool dark = ok && dark_terms_s0(att, n, kd, ks3, ldir, li, attf, true);
+		const f3 t0 = shade_terms_s0(att, n, kd, ks3, ldir, li, attf);
+		const f3 t1 = shade_terms_s0(att, n, kd, ks3, ldir, mul3v(li, kt), attf);
+		y[0] = dark ? 1.f : 0.f;
+		y[1] = t0.x;
+		y[2] = t0.y;
+		y[3] = t0.z;
+		y[4] = t1.x;
+		y[5] = t1.y;
+		y[6] = t1.z;
+	} break;
 	case RTX_KAT_BOX_Q: {
 		/* the walk's setup (shadow_query / shadow_walk) and its box test on the quantised box */
 		const f3 o = ld3(x), d = ld3(x + 3), qo = ld3(x + 12), qs = ld3(x + 15);
@@ -2479,6 +2550,7 @@ __global__ __launch_bounds__(WAVE) void k_kat_order(uint32_t n, const float *__r
 		ks.attenuation = (int32_t)x[34];
 		ks.att_offset = x[35];
 		ks.dark = x[36] != 0.f ? 1u : 0u;
+		ks.spec = 1u; /* the default, as the product's key pass runs */
 		for (int k = 0; k < 3; k++)
 			ks.tf.c[k] = x[30 + k];
 	}
@@ -2696,6 +2768,7 @@ static hipError_t shadow_scene_args(const DScene *S, uint32_t cus, KShadow &ka)
 	/* only where shadow rays walk a tree: against a handful of listed objects the predicate costs
 	 * more than the tests it saves (scene3, RTX_WALK_LINEAR: 59.9 -> 61.7 ms per frame with it) */
 	ka.dark = (S->dark && S->dark_ok && ka.have_tree) ? 1u : 0u;
+	ka.spec = S->spec;
 	ka.num_lin = S->lin ? S->num_lin : 0u;
 	if (walk == WALK_W8) { /* the 8-wide tree's own frame; the emitters it leaves out are tested linearly */
 		for (int a = 0; a < 3; a++) {

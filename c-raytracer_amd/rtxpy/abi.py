@@ -116,8 +116,8 @@ RTX_FRAME_AUTO, RTX_FRAME_WORLD = 0, 1
 RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_OPT_SHADOW_GRAB, \
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
     RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES, \
-    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK, RTX_OPT_SHADOW_ORDER = \
-    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17
+    RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK, RTX_OPT_SHADOW_ORDER, \
+    RTX_OPT_SHADOW_SPEC = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 
@@ -230,11 +230,11 @@ PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target
 # include/rtx_kat.h
 KAT_MOLLER, KAT_SPHERE, KAT_PLANE, KAT_SLAB, KAT_NOISE, KAT_TEXTURE, KAT_SPH_LIGHT, KAT_TRI_LIGHT, \
     KAT_MORTON, KAT_U32, KAT_GI_DIR, KAT_REFRACT, KAT_ANY_TRI, KAT_SPH_LIGHT_SH, KAT_BOX_Q, KAT_SPEC_POW, \
-    KAT_BOX_Q8, KAT_PLANE_CLEAR, KAT_LIN_CLEAR, KAT_DARK, KAT_ORDER = range(21)
-KAT_IN = [16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37]
-KAT_OUT = [2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332]
+    KAT_BOX_Q8, KAT_PLANE_CLEAR, KAT_LIN_CLEAR, KAT_DARK, KAT_ORDER, KAT_SPEC0 = range(22)
+KAT_IN = [16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37, 26]
+KAT_OUT = [2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332, 7]
 KAT_NAMES = ["moller", "sphere", "plane", "slab", "noise", "texture", "sph_light", "tri_light", "morton", "u32",
-             "gi_dir", "refract", "any_tri", "sph_light_sh", "box_q", "spec_pow", "box_q8", "plane_clear", "lin_clear", "dark", "order"]
+             "gi_dir", "refract", "any_tri", "sph_light_sh", "box_q", "spec_pow", "box_q8", "plane_clear", "lin_clear", "dark", "order", "spec0"]
 
 # symbols include/rtx.h declares (checked by tests/test_abi.py)
 RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload_scene", "rtx_render",

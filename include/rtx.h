@@ -369,11 +369,15 @@ enum rtx_option {
 	                               * k_shadow would form them one point per wave (points with 64 light samples
 	                               * or more) and the scene has at most 8 emitters (same masks, same image);
 	                               * 0: k_shadow forms them itself */
-	RTX_OPT_SHADOW_ORDER = 17     /* 1 (default): a shade point that walks the tree takes the light samples of one
+	RTX_OPT_SHADOW_ORDER = 17,    /* 1 (default): a shade point that walks the tree takes the light samples of one
 	                               * emitter, more than 64 and at most 1024 of them, in the order of where their
 	                               * light points lie across the cone toward the emitter (16 buckets), so the 64
 	                               * rays of a packet cross much the same part of the tree; the samples' terms
 	                               * are still added in index order (same image, bit for bit); 0: index order */
+	RTX_OPT_SHADOW_SPEC = 18,     /* 1 (default): a shade point with 64 light samples or more whose material has
+	                               * shininess 0 does not evaluate the specular factor of its samples: powf(x, 0)
+	                               * is 1 for every x, so the specular term is ks li (same image, bit for bit);
+	                               * 0: every sample evaluates it */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no

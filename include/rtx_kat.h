@@ -53,6 +53,10 @@
  *                     RTX_OPT_SHADOW_DARK flag.  n_ord: the samples in the order (0: the run is not ordered),
  *                     order[pos]: the sample at position pos (-1 beyond n_ord), bucket[j]: sample j's bucket
  *                     (16: dark, or j >= nl), x[j]: its key value; scratch: the kernel's own records)
+ * -- k_shadow's shininess-0 forms (rtx_shadow.hip shade_terms_s0 / dark_terms_s0) against the generic ones --
+ * KAT_SPEC0  (21)    KAT_DARK's record (shin is not read)             = 26  dark terms3 terms_kt3 = 7
+ *                    (what KAT_DARK gives for the same record with shin = +-0, bit for bit: the forms
+ *                     RTX_OPT_SHADOW_SPEC runs for a wave-uniform point of shininess 0)
  * Texture records use the params' u32conv for the float->uint32 conversion.
  */
 #ifndef RTX_KAT_H
@@ -80,12 +84,13 @@ enum rtx_kat_kind {
 	RTX_KAT_LIN_CLEAR = 18,
 	RTX_KAT_DARK = 19,
 	RTX_KAT_ORDER = 20,
-	RTX_KAT_NKINDS = 21,
+	RTX_KAT_SPEC0 = 21,
+	RTX_KAT_NKINDS = 22,
 };
 #define RTX_KAT_FIRST_SHADOW RTX_KAT_ANY_TRI /* kinds >= this run in rtx_shadow.hip */
 
-static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37 };
-static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332 };
+static const int rtx_kat_in_width[RTX_KAT_NKINDS] = { 16, 11, 11, 13, 3, 16, 9, 11, 3, 1, 6, 7, 17, 9, 19, 2, 25, 21, 28, 26, 37, 26 };
+static const int rtx_kat_out_width[RTX_KAT_NKINDS] = { 2, 5, 5, 3, 1, 3, 3, 3, 1, 2, 3, 3, 1, 3, 2, 1, 2, 6, 6, 7, 7332, 7 };
 /* KAT_ORDER's output record: 4 header words, order / bucket / x (1024 each), then the kernel's scratch from word
  * RTX_KAT_ORDER_REC on: the shade-point record (24 words), the emitter (64), the material (64), the masks (8) and
  * the wave's slice (4096) */

@@ -595,7 +595,8 @@ int main(int argc, char **argv)
 	std::vector<double> cone_leaf_hist(8, 0.0), cone_depth_hist(16, 0.0), ws_depth(16, 0.0);
 	const int order = getenv("W8SIM_ORDER") ? atoi(getenv("W8SIM_ORDER")) : 0;
 	/* W8SIM_SORT: the order a point's samples are packed in.  0 index order, 1 buckets of the first
-	 * draw, 2.. keys of the light point's position across the cone (see the per-point code) */
+	 * draw, 2.. keys of the light point's position across the cone (see the per-point code: 9 is
+	 * k_shadow's key, 12 .. 18 two-dimensional variants of it) */
 	const int sort_mode = getenv("W8SIM_SORT") ? atoi(getenv("W8SIM_SORT")) : 0;
 	/* the emitter's bounding sphere (k_shadow's emitter_sphere) */
 	auto emitter_ball = [&](double Lc[3], double &lr) {
@@ -837,6 +838,18 @@ int main(int argc, char **argv)
 					key[j] = m;
 					break;
 				}
+				/* 12 .. 18: a second key dimension on top of mode 9 (x toward the tree's centre) */
+				case 12: key[j] = bucket(x, 16) * 4 + std::min(2.0, std::max(0.0, y + 1)); break; /* 16 buckets of x, y sorted inside */
+				case 13: {                                      /* ... the y direction alternating from bucket to bucket */
+					const double bx = bucket(x, 16), yy = std::min(2.0, std::max(0.0, y + 1));
+					key[j] = bx * 4 + (((int)bx & 1) ? 2 - yy : yy);
+					break;
+				}
+				case 14: key[j] = bucket(x, 16) * 2 + (y >= 0 ? 1 : 0); break; /* 16 buckets of x and the sign of y */
+				case 15: key[j] = bucket(x, 8) * 4 + bucket(y, 4); break;      /* 8 x 4 cells */
+				case 16: key[j] = bucket(x, 16) * 4 + bucket(y, 4); break;     /* 16 x 4 cells */
+				case 17: key[j] = bucket(x, 5) * 4 + bucket(y, 4); break;      /* 5 x 4 cells */
+				case 18: key[j] = atan2(y, x); break;                          /* the angle about the axis, full sort */
 				default: key[j] = bucket(x, 8); break;          /* 8: 8 buckets of x */
 				}
 			}
