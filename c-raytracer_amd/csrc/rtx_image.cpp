@@ -209,3 +209,95 @@ extern "C" int rtx_denoise(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_denoise
 	HIP_TRY(hipMemcpy(rgb, c->d_dn_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
 	return RTX_OK;
 }
+
+/* ------------------------------------------------------------------------ */
+/* variance-guided denoiser (include/rtx.h rtx_denoise_variance*)           */
+/* ------------------------------------------------------------------------ */
+extern "C" void rtx_denoise_variance_params_default(rtx_denoise_variance_params *p)
+{
+	if (!p)
+		return;
+	/* chosen by a device sweep over the quality test's frames: sigma_color 1..4 x 1..3 levels, the pair
+	 * with the smallest larger ratio of the two frames; the feature sigmas are rtx_denoise's */
+	p->iterations = 1;
+	p->sigma_color = 3.f;
+	p->sigma_normal = 0.05f;
+	p->sigma_albedo = 0.1f;
+	p->sigma_plane = 0.02f;
+}
+
+static int denoise_variance_check(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_denoise_variance_params *dp, const void *features,
+				  const void *rgb, const void *variance)
+{
+	if (!c || !dp || !features || !rgb || !variance)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (!w || !h || (uint64_t)w * h > RTX_RAYS_MAX)
+		return fail(RTX_ERR_ARG, "bad denoise size %ux%u", w, h);
+	if (dp->iterations < 1 || dp->iterations > 8)
+		return fail(RTX_ERR_ARG, "%u denoise iterations outside 1..8", dp->iterations);
+	for (float s : { dp->sigma_color, dp->sigma_normal, dp->sigma_albedo, dp->sigma_plane })
+		if (!(s > 0.f))
+			return fail(RTX_ERR_ARG, "denoise sigma %g is not above 0", (double)s);
+	return RTX_OK;
+}
+
+/* checked arguments on device buffers; the records share the scratch rtx_denoise grows */
+static int denoise_variance_common(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_denoise_variance_params *dp, const void *d_features,
+				   void *d_rgb, void *d_variance, hipStream_t stream)
+{
+	if ((uintptr_t)d_features & 15u)
+		return fail(RTX_ERR_ARG, "feature buffer must be 16-byte aligned");
+	if (((uintptr_t)d_rgb | (uintptr_t)d_variance) & 3u)
+		return fail(RTX_ERR_ARG, "rgb and variance buffers must be 4-byte aligned");
+	const size_t n = (size_t)w * h;
+	if (c->d_dn_work.grow(7 * n * sizeof(float4)) != hipSuccess)
+		return fail(RTX_ERR_NOMEM, "denoise work buffers of %zu pixels", n);
+	HIP_TRY(c->d_dn_ctr.grow(sizeof(unsigned long long)));
+	HIP_TRY(hipMemsetAsync(c->d_dn_ctr, 0, sizeof(unsigned long long), stream));
+	HIP_TRY(hipEventRecord(c->ev0, stream));
+	HIP_TRY(rtx_launch_denoise_variance(w, h, dp, (const float4 *)d_features, (float *)d_rgb, (float *)d_variance, c->d_dn_work,
+					    c->d_dn_ctr, stream));
+	HIP_TRY(hipEventRecord(c->ev1, stream));
+	unsigned long long hits = 0;
+	HIP_TRY(hipMemcpyAsync(&hits, c->d_dn_ctr, sizeof(hits), hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+	c->dn_stats.filter_ms = ms;
+	c->dn_stats.pixels = n;
+	c->dn_stats.hit_pixels = hits;
+	c->dn_stats.iterations = dp->iterations;
+	return RTX_OK;
+}
+
+extern "C" int rtx_denoise_variance_device(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_denoise_variance_params *dp,
+					   const void *d_features, void *d_rgb, void *d_variance, void *stream)
+{
+	int rc = denoise_variance_check(c, w, h, dp, d_features, d_rgb, d_variance);
+	if (rc)
+		return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	return denoise_variance_common(c, w, h, dp, d_features, d_rgb, d_variance, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int rtx_denoise_variance(rtx_ctx *c, uint32_t w, uint32_t h, const rtx_denoise_variance_params *dp,
+				    const rtx_feature *features, float *rgb, float *variance)
+{
+	int rc = denoise_variance_check(c, w, h, dp, features, rgb, variance);
+	if (rc)
+		return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t n = (size_t)w * h;
+	if (c->d_dn_feat.grow(n * sizeof(rtx_feature)) != hipSuccess || c->d_dn_rgb.grow(n * 3 * sizeof(float)) != hipSuccess ||
+	    c->d_dn_var.grow(n * 3 * sizeof(float)) != hipSuccess)
+		return fail(RTX_ERR_NOMEM, "device copies of %zu pixels", n);
+	HIP_TRY(hipMemcpyAsync(c->d_dn_feat, features, n * sizeof(rtx_feature), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(c->d_dn_rgb, rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(c->d_dn_var, variance, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	rc = denoise_variance_common(c, w, h, dp, c->d_dn_feat, c->d_dn_rgb, c->d_dn_var, c->stream);
+	if (rc)
+		return rc;
+	HIP_TRY(hipMemcpy(rgb, c->d_dn_rgb, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(variance, c->d_dn_var, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+	return RTX_OK;
+}

@@ -203,9 +203,9 @@ struct rtx_ctx : CtxHandles {
 	rtx_shadow_ray_stats shadow_ray_stats{}; /* rtx_trace_shadow_rays */
 	/* denoiser (rtx_frame_features*, rtx_denoise*): grow-only scratch of its own */
 	DevBuf<float4> d_dn_rays, d_dn_hits; /* the frame's rays and their closest hits */
-	DevBuf<float4> d_dn_work;            /* the filter's 16-byte records (rtx_launch_denoise) */
+	DevBuf<float4> d_dn_work;            /* the filter's 16-byte records (rtx_launch_denoise, rtx_launch_denoise_variance) */
 	DevBuf<float4> d_dn_feat;            /* the host-buffer calls' device copies */
-	DevBuf<float> d_dn_rgb;
+	DevBuf<float> d_dn_rgb, d_dn_var;
 	DevBuf<unsigned long long> d_dn_ctr; /* k_dn_pack's hit-pixel count */
 	rtx_denoise_stats dn_stats{};
 	/* multi-pass rendering (rtx_render_passes*): grow-only scratch of its own */

@@ -122,6 +122,12 @@ RTX_HIDDEN hipError_t rtx_launch_denoise(uint32_t w, uint32_t h, const rtx_denoi
 					 float *rgb, float4 *work, unsigned long long *hit_count, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_denoise(void);
 
+/* rtx_denoise_variance.hip */
+RTX_HIDDEN hipError_t rtx_launch_denoise_variance(uint32_t w, uint32_t h, const rtx_denoise_variance_params *dp,
+						  const float4 *feat, float *rgb, float *variance, float4 *work,
+						  unsigned long long *hit_count, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_denoise_variance(void);
+
 /* rtx_passes.hip: the passes of rtx_render_passes* folded into a mean and its variance */
 RTX_HIDDEN uint32_t rtx_pass_blocks(uint64_t n);
 RTX_HIDDEN hipError_t rtx_launch_pass_fold(uint64_t n, uint32_t k, int out, const float *rgb, double *state, float *out_rgb,

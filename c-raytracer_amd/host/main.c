@@ -26,6 +26,9 @@
  *   --adaptive   with --target-error E: each 8x8 tile stops receiving passes once its share of the error
  *                budget is met (rtx_render_adaptive); 16 passes at most unless --passes is given
  *                The multi-pass flags render on one device; --denoise then filters the mean.
+ *   --denoise-variance   with a multi-pass flag: the render also returns the variance of the mean, and the mean
+ *                goes through rtx_frame_features + rtx_denoise_variance (defaults) before it is saved (before
+ *                --denoise, where both are given)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -61,7 +64,8 @@ static const char *HELPTEXT =
 	"[--aa]                           : DEFAULT = OFF     : anti-aliasing: every pass at its own sub-pixel offset (16 passes unless --passes).\n"
 	"[--lens] (float) (float)         : DEFAULT = OFF     : thin lens: aperture radius and focus distance (16 passes unless --passes).\n"
 	"[--target-error] (float)         : DEFAULT = 0       : stop once the passes' error estimate is at most this (one GPU only).\n"
-	"[--adaptive]                     : DEFAULT = OFF     : with --target-error: a tile stops receiving passes once its share of the error is met.\n";
+	"[--adaptive]                     : DEFAULT = OFF     : with --target-error: a tile stops receiving passes once its share of the error is met.\n"
+	"[--denoise-variance]             : DEFAULT = OFF     : with --passes, --aa, --lens, --target-error or --adaptive: filter the mean guided by its variance.\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -156,6 +160,11 @@ int main(int argc, char **argv)
 			pp.passes = 16;
 		multipass = 1;
 	}
+	const int denoise_variance = argv_find(argc, argv, "--denoise-variance", 0) != 0;
+	if (denoise_variance && !multipass) {
+		LOG("--denoise-variance needs a multi-pass flag: --passes, --aa, --lens, --target-error or --adaptive.");
+		return 1;
+	}
 	if (multipass && ngpu > 1) {
 		LOG("--passes, --aa, --lens, --target-error and --adaptive render on one GPU, not on %d.", ngpu);
 		return 1;
@@ -182,8 +191,9 @@ int main(int argc, char **argv)
 	}
 	size_t px = (size_t)w * h;
 	float *rgb = calloc(px * 3, sizeof(float)), *z = calloc(px, sizeof(float));
+	float *var = denoise_variance ? calloc(px * 3, sizeof(float)) : NULL; /* the variance of the passes' mean */
 	int *devs = calloc((size_t)ngpu, sizeof(int));
-	if (!rgb || !z || !devs) {
+	if (!rgb || !z || !devs || (denoise_variance && !var)) {
 		LOG("Unable to allocate the framebuffer.");
 		return 1;
 	}
@@ -201,8 +211,8 @@ int main(int argc, char **argv)
 		rtx_pass_stats ps;
 		rtx_adaptive_stats as;
 		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) ||
-		    (adaptive ? rtx_render_adaptive(ctx, &fr, &p, &pp, rgb, z, NULL, NULL) || rtx_get_adaptive_stats(ctx, &as)
-			      : rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, NULL) || rtx_get_pass_stats(ctx, &ps))) {
+		    (adaptive ? rtx_render_adaptive(ctx, &fr, &p, &pp, rgb, z, var, NULL) || rtx_get_adaptive_stats(ctx, &as)
+			      : rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, var) || rtx_get_pass_stats(ctx, &ps))) {
 			LOG("%s", rtx_last_error());
 			rtx_close(ctx);
 			return 1;
@@ -240,6 +250,30 @@ int main(int argc, char **argv)
 		LOG("Gathered %d shards in %.3f ms.", ngpu, st.gather_ms);
 	LOG("Rays: %llu closest + %llu shadow in %.3f ms device time (%.1f Mrays/s).", (unsigned long long)closest,
 	    (unsigned long long)shadow, kms, kms > 0 ? (closest + shadow) / (kms * 1e3) : 0.0);
+
+	if (denoise_variance) {
+		/* as --denoise below, with the variance the passes gave: both are filtered, the mean is saved */
+		LOG("Denoising with the variance.");
+		rtx_ctx *ctx = NULL;
+		rtx_feature *feat = malloc(px * sizeof(rtx_feature));
+		rtx_denoise_variance_params dp;
+		rtx_denoise_stats ds;
+		rtx_denoise_variance_params_default(&dp);
+		if (!feat) {
+			LOG("Unable to allocate the feature buffer.");
+			return 1;
+		}
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_frame_features(ctx, &fr, p.u32conv, feat) ||
+		    rtx_denoise_variance(ctx, w, h, &dp, feat, rgb, var) || rtx_get_denoise_stats(ctx, &ds)) {
+			LOG("%s", rtx_last_error());
+			rtx_close(ctx);
+			return 1;
+		}
+		rtx_close(ctx);
+		free(feat);
+		LOG("Denoised %llu hit pixels: features %.3f ms, %u variance-guided filter levels %.3f ms.",
+		    (unsigned long long)ds.hit_pixels, ds.features_ms, ds.iterations, ds.filter_ms);
+	}
 
 	if (argv_find(argc, argv, "--denoise", 0)) {
 		/* a context of its own on the first device: the frame's feature records, then the filter with its

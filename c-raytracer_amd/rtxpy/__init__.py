@@ -411,6 +411,40 @@ class Renderer:
         _check(self.lib.rtx_denoise_device(self._ctx, width, height, C.byref(p), C.c_void_p(d_features), C.c_void_p(d_rgb),
                                            C.c_void_p(stream) if stream else None))
 
+    @staticmethod
+    def denoise_variance_params(**params):
+        """rtx_denoise_variance_params_default plus overrides (iterations, sigma_color in standard deviations,
+        sigma_normal / _albedo / _plane)"""
+        p = abi.DenoiseVarianceParams()
+        rtx_lib().rtx_denoise_variance_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    def denoise_variance(self, rgb, variance, features, **params):
+        """rtx_denoise_variance on host arrays: rgb and variance (h, w, 3) float32 (the mean and the variance of the
+        mean of render_passes / render_adaptive), features the (h, w) array of features(); returns the filtered
+        copies (rgb, variance)."""
+        out = np.ascontiguousarray(rgb, dtype=np.float32).copy()
+        var = np.ascontiguousarray(variance, dtype=np.float32).copy()
+        feat = np.ascontiguousarray(features, dtype=abi.FEATURE_DTYPE)
+        h, w = out.shape[:2]
+        if feat.shape != (h, w) or var.shape != out.shape:
+            raise ValueError("features, variance and rgb differ in shape")
+        p = self.denoise_variance_params(**params)
+        _check(self.lib.rtx_denoise_variance(self._ctx, w, h, C.byref(p), feat.ctypes.data, out.ctypes.data, var.ctypes.data))
+        return out, var
+
+    def denoise_variance_device(self, width, height, d_features, d_rgb, d_variance, stream=None, **params):
+        """rtx_denoise_variance_device: d_features / d_rgb / d_variance are device pointers (ints); d_rgb and
+        d_variance are filtered in place."""
+        p = self.denoise_variance_params(**params)
+        _check(self.lib.rtx_denoise_variance_device(self._ctx, width, height, C.byref(p), C.c_void_p(d_features),
+                                                    C.c_void_p(d_rgb), C.c_void_p(d_variance),
+                                                    C.c_void_p(stream) if stream else None))
+
     def denoise_stats(self):
         s = abi.DenoiseStats()
         _check(self.lib.rtx_get_denoise_stats(self._ctx, C.byref(s)))

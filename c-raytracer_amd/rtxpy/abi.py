@@ -198,6 +198,17 @@ FEATURE_DTYPE = [("position", "<f4", 3), ("z", "<f4"), ("normal", "<f4", 3), ("m
 # rtx_denoise_params_default
 DENOISE_DEFAULTS = {"iterations": 1, "sigma_color": 0.004, "sigma_normal": 0.05, "sigma_albedo": 0.1, "sigma_plane": 0.02}
 
+
+class DenoiseVarianceParams(C.Structure):
+    """rtx_denoise_variance_params: sigma_color in standard deviations of a colour difference"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_plane", C.c_float)]
+
+
+# rtx_denoise_variance_params_default
+DENOISE_VARIANCE_DEFAULTS = {"iterations": 1, "sigma_color": 3.0, "sigma_normal": 0.05, "sigma_albedo": 0.1,
+                             "sigma_plane": 0.02}
+
 # multi-pass rendering (rtx_pass_frame, rtx_render_passes*)
 RTX_PASS_JITTER = 1
 RTX_PASSES_MAX = 65536
@@ -251,6 +262,7 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats",
                "rtx_frame_features_device", "rtx_frame_features", "rtx_denoise_params_default", "rtx_denoise_device",
                "rtx_denoise", "rtx_get_denoise_stats",
+               "rtx_denoise_variance_params_default", "rtx_denoise_variance_device", "rtx_denoise_variance",
                "rtx_pass_params_default", "rtx_pass_frame", "rtx_render_passes", "rtx_render_passes_device",
                "rtx_get_pass_stats",
                "rtx_render_tiles", "rtx_render_tiles_device",
@@ -423,6 +435,14 @@ def declare_rtx(lib):
     lib.rtx_denoise.restype = C.c_int
     lib.rtx_get_denoise_stats.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
     lib.rtx_get_denoise_stats.restype = C.c_int
+    lib.rtx_denoise_variance_params_default.argtypes = [C.POINTER(DenoiseVarianceParams)]
+    lib.rtx_denoise_variance_params_default.restype = None
+    lib.rtx_denoise_variance_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarianceParams), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_denoise_variance_device.restype = C.c_int
+    lib.rtx_denoise_variance.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarianceParams), C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.rtx_denoise_variance.restype = C.c_int
     lib.rtx_pass_params_default.argtypes = [C.POINTER(PassParams)]
     lib.rtx_pass_params_default.restype = None
     lib.rtx_pass_frame.argtypes = [C.POINTER(Frame), C.POINTER(PassParams), C.c_uint32, C.POINTER(Frame)]

@@ -667,6 +667,44 @@ typedef struct rtx_denoise_stats {
 int rtx_get_denoise_stats(const rtx_ctx *ctx, rtx_denoise_stats *out);
 
 /*
+ * The variance-guided filter: the same a-trous filter over the mean and the variance of the
+ * mean that rtx_render_passes* / rtx_render_adaptive* write, with the colour distance measured in the pixel's
+ * own estimated noise, so sigma_color is a number of standard deviations and does not depend on the frame's
+ * units or on how many passes a pixel received.  For level k = 0 .. iterations-1, step s = 2^k, with c the
+ * level's input colour, V its per-channel variance and f the features: a pixel is live iff f.z != 0, c is
+ * finite and every component of V is finite and >= 0.  A pixel that is not live keeps the bits of its colour
+ * and its variance, and no tap reads it.  For a live pixel i:
+ *     g_i = the mean of V_r + V_g + V_b over the adjacent (step 1 at every level) live pixels inside the
+ *           frame, weights b[u] b[v], b = (1/4, 1/2, 1/4), normalised by the weights of the taps used
+ * and over the taps (u, v) in {-2..2}^2 with j = i + (u s, v s) inside the frame and live:
+ *     e_c = 0 if |c_i-c_j|^2 == 0, else |c_i-c_j|^2 / (sigma_color^2 2 g_i)      (+inf where g_i == 0)
+ *     e   = e_c + |n_i-n_j|^2 / sigma_normal^2 + |a_i-a_j|^2 / sigma_albedo^2
+ *         + (n_i . (P_j-P_i))^2 / (sigma_plane z_i)^2
+ *     w   = h[u] h[v] exp(-e),  h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *     c'_i = c_i + sum w (c_j-c_i) / sum w,     V'_i = sum w^2 V_j / (sum w)^2  (per channel)
+ * sigma_color is the same at every level: the shrinking V tightens it.  The 2 is the variance of a difference
+ * of two equally noisy estimates.  An all-zero variance (one pass, a deterministic frame) returns the colour's
+ * bits.  The variance handed back guides the next level and underestimates the filtered frame's real error
+ * after the first level, as the taps are no longer independent: it is not an error bar.  Deterministic: two
+ * runs give the same bits.  Needs no uploaded scene.
+ */
+typedef struct rtx_denoise_variance_params {
+	uint32_t iterations;      /* 1..8, default 1 */
+	float sigma_color;        /* in standard deviations of a colour difference, > 0; INFINITY = term off.  Default 3 */
+	float sigma_normal, sigma_albedo, sigma_plane;   /* as rtx_denoise_params, the same defaults */
+} rtx_denoise_variance_params;
+void rtx_denoise_variance_params_default(rtx_denoise_variance_params *p);
+/* d_features: w * h rtx_feature records, d_rgb and d_variance: 3 floats per pixel each, both in/out, in the layouts
+ * rtx_render_passes_device writes; DEVICE buffers (d_features 16-byte aligned), enqueued on `stream` (NULL = the
+ * context's own); synchronises it.  Errors as rtx_denoise_device, and RTX_ERR_ARG for a null d_variance.  Fills
+ * rtx_denoise_stats (filter_ms, iterations, pixels, hit_pixels) as rtx_denoise_device does. */
+int rtx_denoise_variance_device(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_denoise_variance_params *params,
+				const void *d_features, void *d_rgb, void *d_variance, void *stream);
+/* Same on HOST buffers. */
+int rtx_denoise_variance(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_denoise_variance_params *params,
+			 const rtx_feature *features, float *rgb, float *variance);
+
+/*
  * Multi-pass rendering: the frame rendered K times and the passes combined on the device
  * into a per-pixel mean and the variance of that mean.  Pass k has its own seed (params->seed + k), its own
  * sub-pixel offset (anti-aliasing) and its own lens point (a thin lens).  k_trace forms a pixel's ray from
