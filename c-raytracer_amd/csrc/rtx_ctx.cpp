@@ -237,6 +237,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow pre-mask %lld is not 0 or 1", (long long)value);
 		c->opt_premask = (int)value;
 		return RTX_OK;
+	case RTX_OPT_TRACE_PACK:
+		if (value != 0 && value != 1 && value != 512 && value != 1024 && value != 2048 && value != 4096)
+			return fail(RTX_ERR_ARG, "trace pack %lld is not 0, 1, 512, 1024, 2048 or 4096", (long long)value);
+		c->opt_trace_pack = (uint32_t)value;
+		return RTX_OK;
 	}
 	return fail(RTX_ERR_ARG, "unknown option %d", option);
 }

@@ -122,6 +122,11 @@ struct PhaseClock {};
 #define PHASE(clk, what, st) ((void)clk)
 #endif
 
+/* RTX_OPT_TRACE_PACK 1: the rays of a segment of k_trace's packed GI walk (the sweep) */
+#ifndef RTX_TRACE_PACK_SEG
+#define RTX_TRACE_PACK_SEG 4096u
+#endif
+
 /* the settings a render's shade points per tile depend on (rtx_ctx.sp_tile_key) */
 struct SpKey {
 	uint32_t v[21] = {};
@@ -170,6 +175,7 @@ struct rtx_ctx : CtxHandles {
 	bool have_scene = false;
 	/* work buffers (grow-only) */
 	DevBuf<DTask> d_tasks;
+	DevBuf<void> d_pack;        /* k_trace's packed GI walk: a result table and a walk queue per wave (RTX_OPT_TRACE_PACK) */
 	DevBuf<uint32_t> d_ostk;    /* k_trace lane-stack overflow (DScene.ostk) */
 	DevBuf<uint32_t> d_w8spill; /* k_shadow lane-stack spill of deep 8-wide trees (DScene.w8spill) */
 	DevBuf<float4> d_staging;
@@ -243,6 +249,7 @@ struct rtx_ctx : CtxHandles {
 	int opt_spec = 1;         /* RTX_OPT_SHADOW_SPEC: a shininess-0 point's samples skip the specular factor */
 	int opt_order = 1;        /* RTX_OPT_SHADOW_ORDER: a walking point's light samples walked in key order */
 	int opt_premask = 1;      /* RTX_OPT_SHADOW_PREMASK: the per-point masks formed before k_shadow, one point per lane */
+	uint32_t opt_trace_pack = 1; /* RTX_OPT_TRACE_PACK: 0 off, 1 RTX_TRACE_PACK_SEG rays per segment, else that many */
 	uint32_t mem_share = 1;  /* contexts sharing this device's HBM at once (a loopback group's n): the shade-point
 	                           * budget of a render is a third of the free HBM divided by it */
 };

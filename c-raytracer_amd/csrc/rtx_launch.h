@@ -51,13 +51,16 @@ hipError_t rtx_w8_collapse_device(const DNode *recs, uint32_t nnodes, uint32_t n
 RTX_HIDDEN hipError_t rtx_load_wide8_dev(void);
 
 /* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays.  tile_list: the device list of a tile-list render
- * (rtx_render_tiles*), indexed by the chunk positions tile_begin..; null: the shard of P */
+ * (rtx_render_tiles*), indexed by the chunk positions tile_begin..; null: the shard of P.  pack: the packed GI
+ * walk's region (RTX_OPT_TRACE_PACK), waves * rtx_trace_pack_bytes(pack_seg) bytes, for a scene that walks the
+ * 8-wide tree (S->trace_w8); null: every GI batch walks on its own */
+size_t rtx_trace_pack_bytes(uint32_t pack_seg);
 size_t rtx_trace_lds_bytes(uint32_t stack_size);
 hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu);
 hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const DParams *P, float *rgb, float *z, DTask *tasks,
 			    uint32_t task_cap, float4 *staging, uint32_t staging_cap, float4 *sp_out, uint32_t sp_cap,
 			    uint2 *tile_rec, uint32_t tile_begin, uint32_t tile_end, unsigned long long *ctr, uint32_t waves,
-			    int count, const uint32_t *tile_list, hipStream_t stream);
+			    int count, const uint32_t *tile_list, void *pack, uint32_t pack_seg, hipStream_t stream);
 hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec, const float4 *contrib,
 			    uint32_t tile_begin, uint32_t ntiles, float *rgb, const uint32_t *tile_list, hipStream_t stream);
 size_t rtx_rays_lds_bytes(uint32_t stack_size);

@@ -100,6 +100,11 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	HIP_TRY(c->d_tasks.grow((size_t)waves * task_cap * sizeof(DTask)));
 	HIP_TRY(rtx_ensure_ostk(c, waves)); /* the closest-hit stack entries beyond the LDS part */
 	c->scene.trace_w8 = (c->scene.w8 && c->opt_trace_walk != RTX_WALK_BVH2) ? 1u : 0u;
+	/* RTX_OPT_TRACE_PACK: path GI on the 8-wide tree takes the packed instances, a region per wave */
+	const uint32_t pack_seg = c->opt_trace_pack == 1 ? RTX_TRACE_PACK_SEG : c->opt_trace_pack;
+	const bool pack = pack_seg && c->scene.trace_w8 && P.gi == RTX_GI_PATH;
+	if (pack)
+		HIP_TRY(c->d_pack.grow((size_t)waves * rtx_trace_pack_bytes(pack_seg)));
 	c->stats.trace_walk = c->scene.trace_w8 ? RTX_WALK_W8 : RTX_WALK_BVH2;
 	HIP_TRY(rtx_ensure_w8spill(c, c->scene));
 
@@ -143,7 +148,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		HIP_TRY(hipEventRecord(c->ev[0], stream));
 		HIP_TRY(rtx_launch_trace(&c->scene, &F, &P, d_rgb, d_z, c->d_tasks, task_cap, c->d_staging,
 					 (uint32_t)staging_cap, c->d_sp, sp_cap, c->d_tile_rec, begin, end, c->d_ctr,
-					 std::min<uint32_t>(waves, end - begin), p->count_traversal, d_tiles, stream));
+					 std::min<uint32_t>(waves, end - begin), p->count_traversal, d_tiles,
+					 pack ? (void *)c->d_pack : nullptr, pack_seg, stream));
 		HIP_TRY(hipEventRecord(c->ev[1], stream));
 		unsigned long long head[RTX_C_N];
 		HIP_TRY(hipMemcpyAsync(head, c->d_ctr, sizeof(head), hipMemcpyDeviceToHost, stream));

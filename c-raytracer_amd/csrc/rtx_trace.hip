@@ -8,7 +8,8 @@
  *           closest-hit query of the tile's ray trees: primaries, then
  *           reflection/refraction children from a per-wave LIFO task stack in HBM
  *           (__ballot/mbcnt compaction on push), and the path-GI samples of each
- *           batch flattened over (hit, sample) 64 at a time.  Per-lane BVH2
+ *           batch flattened over (hit, sample) 64 at a time (on the 8-wide tree in segments, the
+ *           rays that go past the root packed 64 to a wave: gi_batch_packed).  Per-lane BVH2
  *           traversal with the stack in LDS ([entry][lane], conflict-free).  Local
  *           terms (ke, ambient) go straight to the tile's pixels; every hit that
  *           sees lights becomes a 96-byte shade point (rtx_wave.h), appended in a
@@ -206,10 +207,14 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 /* FAR: some lane of the wave has a far origin (t0 and the per-lane far flag live across the walk);
  * the other instances take t0 = 0 and no far lane as constants, so the waves of near rays (all of
  * them in the reference scenes' views) keep those registers for the walk */
-template <bool COUNT, int OCT, bool FAR, bool ANY = false>
+/* ONE / node / grp / left (the packed GI walk, gi_batch_packed): ONE makes the one visit of `node` and
+ * leaves the walk's state in *left (x the next node or RTX_NONE, y the kept group; the lane stack is
+ * empty after a first visit); a walk entered at (node, grp) with the ray's tbest / hid so far is that
+ * walk resumed.  The defaults are the whole walk from the root. */
+template <bool COUNT, int OCT, bool FAR, bool ANY = false, bool ONE = false>
 __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uint32_t *ostk, size_t ostride, f3 o, f3 d,
 					      f3 ob, f3 inv, float t0_, bool far_, float &tbest, uint32_t &hid,
-					      TraceCount &tc)
+					      TraceCount &tc, uint32_t node = 0, uint32_t grp = 0, uint2 *left = nullptr)
 {
 	const float t0 = FAR ? t0_ : 0.f;
 	const bool far = FAR && far_;
@@ -234,7 +239,6 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 	const f3 invq = mk3(inv.x / qs.x, inv.y / qs.y, inv.z / qs.z);
 	const f3 oq = mk3((ob.x - qo.x) * qs.x, (ob.y - qo.y) * qs.y, (ob.z - qo.z) * qs.z);
 	const f3 oi = mul3v(oq, invq);
-	uint32_t node = 0, grp = 0;
 	float gt = -INFINITY; /* RTX_TRACE_CULL: least entry distance of the group in grp (-inf: unknown) */
 	constexpr bool T = RTX_TRACE_NEAR || RTX_TRACE_CULL;
 	while (node != RTX_NONE) {
@@ -326,13 +330,22 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 				node = RTX_NONE;
 			}
 		}
+		if (ONE)
+			break;
 	}
+	if (ONE)
+		*left = make_uint2(node, grp);
 }
 
-template <bool COUNT, bool ANY = false, bool LIM = false>
+/* ROOT (the packed GI walk's classify loop): a wave that would take the generic near instance makes the
+ * root visit alone and leaves each lane's walk state in *left (x = RTX_NONE: this lane's walk is over);
+ * a wave with a far lane or of one octant walks to the end as ever, and *left says so for every lane. */
+template <bool COUNT, bool ANY = false, bool LIM = false, bool ROOT = false>
 __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o, f3 d, uint32_t inside, float &t_out,
-				 uint32_t &hid_out, TraceCount &tc)
+				 uint32_t &hid_out, TraceCount &tc, uint2 *left = nullptr)
 {
+	if (ROOT)
+		*left = make_uint2(RTX_NONE, 0u);
 	float tbest = LIM ? t_out : FLT_MAX;
 	uint32_t hid = RTX_NONE;
 	if (act && isnan3(d)) /* TIR / degenerate directions hit nothing */
@@ -429,13 +442,32 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 				RTX_CWALK(7)
 #undef RTX_CWALK
 			default:
-				closest_walk8<COUNT, 8, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
+				if constexpr (ROOT)
+					closest_walk8<COUNT, 8, false, ANY, true>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest,
+										  hid, tc, 0u, 0u, left);
+				else
+					closest_walk8<COUNT, 8, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
 				break;
 			}
 		}
 	}
 	t_out = tbest;
 	hid_out = hid;
+}
+
+/* The rest of a generic near walk that trace_closest_w8<..., ROOT> left at `at` after the root visit, with
+ * the ray's closest hit so far in tbest / hid: the same frame transform, and every visit and test the whole
+ * walk would have made from there (a lane's walk never depends on the lanes beside it). */
+template <bool COUNT>
+__device__ __forceinline__ void resume_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o, f3 d, uint2 at,
+						  float &tbest, uint32_t &hid, TraceCount &tc)
+{
+	const bool rot = S.tf.rotated != 0;
+	const f3 ob = rot ? tf_point(S.tf.r, S.tf.c, o) : o;
+	const f3 inv = safe_inv_fast(rot ? tf_dir(S.tf.r, d) : d);
+	if (act)
+		closest_walk8<COUNT, 8, false>(S, (lds_u32 *)stk, S.ostk + (size_t)blockIdx.x * WAVE, (size_t)gridDim.x * WAVE, o,
+					       d, ob, inv, 0.f, false, tbest, hid, tc, at.x, at.y);
 }
 
 /* the closest-hit walk of this scene: the 8-wide tree when built and chosen (DScene.trace_w8) */
@@ -593,6 +625,58 @@ __device__ __forceinline__ void emit_sp(TraceOut &T, bool has, const ShadePt &s)
 		T.overflow = true;
 }
 
+/* a GI ray's hit (child cast_ray(..., 0 bounces)): its local term to its parent's pixel, its shade point emitted */
+__device__ __forceinline__ void gi_shade(const DScene &S, const DParams &P, uint32_t total_lights, bool act,
+					 const GiParent &par, f3 dir, f3 kr, uint64_t ckey, float t, uint32_t hid, f3 &acc,
+					 TraceOut &T)
+{
+	const bool hit = act && hid != RTX_NONE;
+	ShadePt cs = ShadePt();
+	f3 cc = mk3(0.f, 0.f, 0.f);
+	bool has = false;
+	if (hit) {
+		/* child cast_ray(..., 0 bounces): ke + direct light only (path mode has no ambient term) */
+		const HitInfo hi = hit_info(S, hid, par.p, dir, t);
+		const DMaterial &m = S.mats[hi.mat];
+		const f3 w = mul3s(kr, att_factor(P, t));
+		cc = mul3v(w, ld3(m.ke));
+		cs.nl = hi.outside ? lights_for(S, total_lights, hi.obj) : 0u;
+		has = cs.nl != 0;
+		cs.p = hi.p;
+		cs.n = hi.n;
+		cs.d = dir;
+		cs.w = w;
+		cs.mat = hi.mat;
+		cs.obj = hi.obj | (has ? sp_far(S.tf, hi.p) : 0u);
+		cs.slot = par.slot;
+		cs.tex = has ? texture_color(m, hi.p, P.u32conv) : mk3(0.f, 0.f, 0.f);
+		cs.key_lo = (uint32_t)ckey;
+		cs.key_hi = (uint32_t)(ckey >> 32);
+	}
+	route_add(acc, hit, par.slot, cc);
+	emit_sp(T, has, cs);
+}
+
+/* ray idx of a batch's flattened (hit, sample) range (render.c:238-288) */
+struct GiRay {
+	GiParent par;
+	uint32_t s;
+	uint64_t pkey;
+	f3 dir;
+};
+__device__ __forceinline__ GiRay gi_ray(const DParams &P, const float *gp_tab, const uint32_t *off, bool act, uint32_t idx)
+{
+	GiRay r;
+	const uint32_t h = act ? owner_of(off, idx) : 0u;
+	r.par = gp_load(gp_tab, h);
+	r.s = idx - off[h];
+	r.pkey = key_of(r.par.key_lo, r.par.key_hi);
+	float u1, u2;
+	draw(P, r.pkey, RTX_STREAM_GI, r.s, u1, u2);
+	r.dir = gi_direction(r.par.n, r.par.eps, u1, u2);
+	return r;
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void gi_batch(const DScene &S, const DParams &P, uint32_t total_lights, uint32_t *stk,
 					 float *gp_tab, uint32_t *off, uint32_t ngi_mine, f3 &acc, TraceOut &T,
@@ -610,47 +694,112 @@ __device__ __forceinline__ void gi_batch(const DScene &S, const DParams &P, uint
 	for (uint32_t base = 0; base < total; base += WAVE) {
 		const uint32_t idx = base + lane_id();
 		const bool act = idx < total;
-		const uint32_t h = act ? owner_of(off, idx) : 0u;
-		const GiParent par = gp_load(gp_tab, h);
-		const uint32_t s = idx - off[h];
-		const uint64_t pkey = key_of(par.key_lo, par.key_hi);
-		float u1, u2;
-		draw(P, pkey, RTX_STREAM_GI, s, u1, u2);
+		const GiRay r = gi_ray(P, gp_tab, off, act, idx);
 		/* render.c:270-286: uniform hemisphere sample about n, weight delta * (n . dir) */
-		const f3 dir = gi_direction(par.n, par.eps, u1, u2);
-		const f3 kr = mul3s(par.w, par.delta * dot3(par.n, dir));
-		const uint64_t ckey = rtx_key_child(pkey, RTX_CHILD_GI0 + s);
+		const f3 kr = mul3s(r.par.w, r.par.delta * dot3(r.par.n, r.dir));
+		const uint64_t ckey = rtx_key_child(r.pkey, RTX_CHILD_GI0 + r.s);
 		float t;
 		uint32_t hid;
-		trace_closest<COUNT>(S, stk, act, par.p, dir, RTX_NONE, t, hid, tc);
+		trace_closest<COUNT>(S, stk, act, r.par.p, r.dir, RTX_NONE, t, hid, tc);
 		n_closest += popc64(ballot(act));
-		const bool hit = act && hid != RTX_NONE;
-		ShadePt cs = ShadePt();
-		f3 cc = mk3(0.f, 0.f, 0.f);
-		bool has = false;
-		if (hit) {
-			/* child cast_ray(..., 0 bounces): ke + direct light only (path mode has no ambient term) */
-			const HitInfo hi = hit_info(S, hid, par.p, dir, t);
-			const DMaterial &m = S.mats[hi.mat];
-			const f3 w = mul3s(kr, att_factor(P, t));
-			cc = mul3v(w, ld3(m.ke));
-			cs.nl = hi.outside ? lights_for(S, total_lights, hi.obj) : 0u;
-			has = cs.nl != 0;
-			cs.p = hi.p;
-			cs.n = hi.n;
-			cs.d = dir;
-			cs.w = w;
-			cs.mat = hi.mat;
-			cs.obj = hi.obj | (has ? sp_far(S.tf, hi.p) : 0u);
-			cs.slot = par.slot;
-			cs.tex = has ? texture_color(m, hi.p, P.u32conv) : mk3(0.f, 0.f, 0.f);
-			cs.key_lo = (uint32_t)ckey;
-			cs.key_hi = (uint32_t)(ckey >> 32);
-		}
-		route_add(acc, hit, par.slot, cc);
-		emit_sp(T, has, cs);
+		gi_shade(S, P, total_lights, act, r.par, r.dir, kr, ckey, t, hid, acc, T);
 		lds_sync();
 	}
+}
+
+/* The packed GI walk (RTX_OPT_TRACE_PACK): PACK = true, a wave's result table and walk queue in HBM and the
+ * rays per segment (a multiple of 64); PACK = false, no argument.  A kernel argument of the true instances
+ * alone, like TileList.  The host takes these instances only for a scene that walks the 8-wide tree. */
+template <bool PACK> struct TracePack {};
+template <> struct TracePack<true> {
+	unsigned char *__restrict__ buf; /* per wave: seg results (t, hid), then seg queue entries of 16 bytes */
+	uint32_t seg;
+};
+#define RTX_PACK_BYTES 24 /* per ray of a wave's region: the result (8) and a queue entry (16) */
+
+/* gi_batch with the deep walks packed.  In a batch of 64 hemisphere directions few rays meet the mesh, and
+ * the whole wave waits on their walks; so the range is taken in segments of `seg` rays, and a segment in
+ * three loops over a per-wave table in HBM:
+ *   classify  every batch as gi_batch forms it, up to the root visit (trace_closest_w8<..., ROOT>); the
+ *             closest hit so far goes to the ray's table entry, and a lane the root visit left with a node
+ *             to visit appends (idx, node, group) to the queue, compacted in index order;
+ *   walk      the queue in packets of 64: the ray formed again, its walk resumed from the stored state;
+ *   emit      every batch in index order again, the ray formed again, with its (t, hid) from the table, and
+ *             gi_batch's tail.
+ * (Keeping the directions in the table too, 12 bytes more per ray, measured no faster than forming them again.)
+ * A ray makes the visits and tests it made in gi_batch, and route_add and emit_sp see the same values in
+ * the same order, so the pixels, the shade points and the counters are gi_batch's bit for bit.  A batch
+ * with a far lane, or of one octant, walks to the end in the classify loop (its instances differ). */
+template <bool COUNT>
+__device__ __forceinline__ void gi_batch_packed(const DScene &S, const DParams &P, uint32_t total_lights, uint32_t *stk,
+						float *gp_tab, uint32_t *off, uint32_t ngi_mine, f3 &acc, TraceOut &T,
+						TraceCount &tc, u64 &n_closest, const TracePack<true> &pack)
+{
+	static_assert(!RTX_TRACE_CULL, "the queue does not carry the kept group's entry distance");
+	uint32_t total;
+	const uint32_t ex = wave_excl_scan(ngi_mine, &total);
+	if (total == 0)
+		return;
+	lds_sync();
+	off[lane_id()] = ex;
+	if (lane_id() == 0)
+		off[WAVE] = total;
+	lds_sync();
+	uint2 *res = (uint2 *)(pack.buf + (size_t)blockIdx.x * pack.seg * RTX_PACK_BYTES);
+	uint4 *queue = (uint4 *)(res + pack.seg);
+	for (uint32_t s0 = 0; s0 < total; s0 += pack.seg) {
+		const uint32_t s1 = min(total, s0 + pack.seg);
+		uint32_t nq = 0;
+		for (uint32_t base = s0; base < s1; base += WAVE) {
+			const uint32_t idx = base + lane_id();
+			const bool act = idx < total;
+			const GiRay r = gi_ray(P, gp_tab, off, act, idx);
+			float t;
+			uint32_t hid;
+			uint2 left;
+			trace_closest_w8<COUNT, false, false, true>(S, stk, act, r.par.p, r.dir, RTX_NONE, t, hid, tc, &left);
+			n_closest += popc64(ballot(act));
+			if (act)
+				res[idx - s0] = make_uint2(__float_as_uint(t), hid);
+			const bool more = left.x != RTX_NONE;
+			const u64 m = ballot(more);
+			if (more)
+				queue[nq + mbcnt(m)] = make_uint4(idx, left.x, left.y, 0u);
+			nq += popc64(m);
+			lds_sync();
+		}
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+		for (uint32_t qb = 0; qb < nq; qb += WAVE) {
+			const bool act = qb + lane_id() < nq;
+			uint4 e = make_uint4(s0, RTX_NONE, 0u, 0u);
+			if (act)
+				e = queue[qb + lane_id()];
+			const GiRay r = gi_ray(P, gp_tab, off, act, e.x);
+			uint2 th = make_uint2(0u, RTX_NONE);
+			if (act)
+				th = res[e.x - s0];
+			float t = __uint_as_float(th.x);
+			resume_closest_w8<COUNT>(S, stk, act, r.par.p, r.dir, make_uint2(e.y, e.z), t, th.y, tc);
+			if (act)
+				res[e.x - s0] = make_uint2(__float_as_uint(t), th.y);
+			lds_sync();
+		}
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+		for (uint32_t base = s0; base < s1; base += WAVE) {
+			const uint32_t idx = base + lane_id();
+			const bool act = idx < total;
+			const GiRay r = gi_ray(P, gp_tab, off, act, idx);
+			uint2 th = make_uint2(0u, RTX_NONE);
+			if (act)
+				th = res[idx - s0];
+			/* render.c:270-286: uniform hemisphere sample about n, weight delta * (n . dir) */
+			const f3 kr = mul3s(r.par.w, r.par.delta * dot3(r.par.n, r.dir));
+			const uint64_t ckey = rtx_key_child(r.pkey, RTX_CHILD_GI0 + r.s);
+			gi_shade(S, P, total_lights, act, r.par, r.dir, kr, ckey, __uint_as_float(th.x), th.y, acc, T);
+		}
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+	}
+	lds_sync();
 }
 
 /* The tiles of a launch: LIST = false, the arithmetic shard tile_offset + pos * tile_stride of DParams, and no
@@ -662,7 +811,7 @@ template <> struct TileList<true> {
 	const uint32_t *__restrict__ p;
 };
 
-template <bool COUNT, bool LIST>
+template <bool COUNT, bool LIST, bool PACK>
 #ifndef RTX_TRACE_OCC
 #define RTX_TRACE_OCC 6 /* waves per SIMD k_trace is register-capped for (80 VGPRs; with 9 LDS stack entries, 24 waves per CU) */
 #endif
@@ -671,7 +820,7 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 						float4 *__restrict__ staging, uint32_t staging_cap,
 						float4 *__restrict__ sp_out, uint32_t sp_cap, uint2 *__restrict__ tile_rec,
 						uint32_t tile_begin, uint32_t tile_end, unsigned long long *__restrict__ ctr,
-						TileList<LIST> tile_list)
+						TileList<LIST> tile_list, TracePack<PACK> pack)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	float *gp_tab = (float *)lds_raw;
@@ -827,8 +976,12 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 				lds_sync();
 				if (hit)
 					gp_store(gp_tab, lane_id(), gp);
-				gi_batch<COUNT>(S, P, total_lights, stk, gp_tab, off, hit ? gp.ngi : 0u, acc, T, tc,
-						n_closest);
+				if constexpr (PACK)
+					gi_batch_packed<COUNT>(S, P, total_lights, stk, gp_tab, off, hit ? gp.ngi : 0u, acc, T,
+							       tc, n_closest, pack);
+				else
+					gi_batch<COUNT>(S, P, total_lights, stk, gp_tab, off, hit ? gp.ngi : 0u, acc, T, tc,
+							n_closest);
 			}
 			if (top == 0)
 				break;
@@ -1194,9 +1347,14 @@ extern "C" size_t rtx_trace_lds_bytes(uint32_t stack_size)
 	return (size_t)WAVE * SPW * 4 + 80 * 4 + lstk * WAVE * 4 + pad;
 }
 
+extern "C" size_t rtx_trace_pack_bytes(uint32_t pack_seg)
+{
+	return (size_t)pack_seg * RTX_PACK_BYTES;
+}
+
 extern "C" hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu)
 {
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_trace<false, false>, WAVE,
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_trace<false, false, false>, WAVE,
 							     rtx_trace_lds_bytes(stack_size));
 }
 
@@ -1204,12 +1362,22 @@ extern "C" hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const D
 				       DTask *tasks, uint32_t task_cap, float4 *staging, uint32_t staging_cap,
 				       float4 *sp_out, uint32_t sp_cap, uint2 *tile_rec, uint32_t tile_begin,
 				       uint32_t tile_end, unsigned long long *ctr, uint32_t waves, int count,
-				       const uint32_t *tile_list, hipStream_t stream)
+				       const uint32_t *tile_list, void *pack, uint32_t pack_seg, hipStream_t stream)
 {
 	const size_t lds = rtx_trace_lds_bytes(S->stack_size);
-#define RTX_TRACE_LAUNCH(C, L, ...) \
-	hipLaunchKernelGGL((k_trace<C, L>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, task_cap, staging, \
-			   staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ })
+	if (pack && (!S->trace_w8 || !pack_seg || pack_seg % WAVE)) /* the packed instances walk the 8-wide tree alone */
+		return hipErrorInvalidValue;
+#define RTX_TRACE_LAUNCH(C, L, ...)                                                                                            \
+	do {                                                                                                                    \
+		if (pack)                                                                                                       \
+			hipLaunchKernelGGL((k_trace<C, L, true>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,  \
+					   task_cap, staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr,     \
+					   TileList<L>{ __VA_ARGS__ }, TracePack<true>{ (unsigned char *)pack, pack_seg });        \
+		else                                                                                                            \
+			hipLaunchKernelGGL((k_trace<C, L, false>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, \
+					   task_cap, staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr,     \
+					   TileList<L>{ __VA_ARGS__ }, TracePack<false>{});                                        \
+	} while (0)
 	if (tile_list && count)
 		RTX_TRACE_LAUNCH(true, true, tile_list);
 	else if (tile_list)

@@ -117,7 +117,7 @@ RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
     RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES, \
     RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK, RTX_OPT_SHADOW_ORDER, \
-    RTX_OPT_SHADOW_SPEC = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18
+    RTX_OPT_SHADOW_SPEC, RTX_OPT_TRACE_PACK = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 

@@ -378,6 +378,12 @@ enum rtx_option {
 	                               * shininess 0 does not evaluate the specular factor of its samples: powf(x, 0)
 	                               * is 1 for every x, so the specular term is ks li (same image, bit for bit);
 	                               * 0: every sample evaluates it */
+	RTX_OPT_TRACE_PACK = 19,      /* 1 (default): k_trace takes a tile's path-GI rays, on the 8-wide tree, in
+	                               * segments: every ray up to its visit of the root, then the rays that go on
+	                               * into the tree packed 64 to a wave, then the hits in the rays' own order (same
+	                               * image, shade points and counters, bit for bit); 512, 1024, 2048 or 4096: the
+	                               * same with that many rays per segment (1 takes the library's own figure);
+	                               * 0: every batch of 64 rays walks to the end on its own */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
