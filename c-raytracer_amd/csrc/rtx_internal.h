@@ -216,7 +216,8 @@ struct rtx_ctx : CtxHandles {
 	rtx_denoise_stats dn_stats{};
 	/* multi-pass rendering (rtx_render_passes*): grow-only scratch of its own */
 	DevBuf<float> d_pass_rgb;     /* the pass being rendered */
-	DevBuf<double> d_pass_state;  /* mean r, g, b and m2 r, g, b, one double per pixel each (rtx_passes.hip) */
+	DevBuf<double> d_pass_state;  /* mean r, g, b and m2 r, g, b, one double per pixel each (rtx_passes.hip); the
+	                               * filtered fold's seventh plane, the weight sum, follows them (rtx_filter.hip) */
 	DevBuf<double> d_pass_sums;   /* the blocks' partial sums of the error, then their two totals */
 	DevBuf<float> d_pass_var;     /* the host-buffer call's device copy of the variance */
 	rtx_pass_stats pass_stats{};
@@ -342,6 +343,12 @@ RTX_HIDDEN int rtx_rays_common(rtx_ctx *c, uint32_t n, const void *d_rays, void 
 
 /* rtx_passes.cpp: what the multi-pass (adaptive: and the adaptive) entries refuse about non-null arguments */
 RTX_HIDDEN int rtx_passes_args_check(const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive);
+/* ... everything they refuse before they launch anything, null arguments and a scene-less context included;
+ * what rtx_pass_frame refuses about the pass parameters alone; and pass k's sub-pixel offset in pixel units
+ * (the filtered entries share all three, rtx_filter.cpp) */
+RTX_HIDDEN int rtx_passes_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive);
+RTX_HIDDEN int rtx_pass_params_check(const rtx_pass_params *pp);
+RTX_HIDDEN void rtx_pass_offset(const rtx_pass_params *pp, uint32_t k, double *ox, double *oy);
 
 /* Steps that more than one entry point takes.  They return the HIP error and each caller reports it
  * with its own code and text. */

@@ -135,7 +135,18 @@ RTX_HIDDEN hipError_t rtx_load_denoise_variance(void);
 RTX_HIDDEN uint32_t rtx_pass_blocks(uint64_t n);
 RTX_HIDDEN hipError_t rtx_launch_pass_fold(uint64_t n, uint32_t k, int out, const float *rgb, double *state, float *out_rgb,
 					   float *out_var, double *partials, double *sums, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_pass_error(uint32_t blocks, const double *partials, double *sums, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_passes(void);
+
+/* rtx_filter.hip: the passes of rtx_render_passes_filtered* folded through a 5x5 reconstruction filter */
+struct rtx_filter_weights {
+	double wx[RTX_FILTER_TAPS], wy[RTX_FILTER_TAPS];
+};
+RTX_HIDDEN uint64_t rtx_filter_blocks(uint32_t w, uint32_t h);
+RTX_HIDDEN hipError_t rtx_launch_pass_filter_fold(uint32_t w, uint32_t h, uint32_t k, int out, const rtx_filter_weights *fw,
+						  const float *rgb, double *state, float *out_rgb, float *out_var, double *partials,
+						  double *sums, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_filter(void);
 
 /* rtx_adaptive.hip: a device tile list's check, and the per-tile state of rtx_render_adaptive* */
 RTX_HIDDEN hipError_t rtx_launch_tiles_check(const uint32_t *tiles, uint32_t n, uint32_t total, uint32_t *flag, hipStream_t stream);

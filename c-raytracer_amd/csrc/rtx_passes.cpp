@@ -37,7 +37,8 @@ static double radical_inverse(uint32_t k, uint32_t b)
 	return r;
 }
 
-static int pass_params_check(const rtx_pass_params *pp)
+/* what rtx_pass_frame refuses about the pass parameters alone (rtx_pass_filter_weights too, rtx_filter.cpp) */
+int rtx_pass_params_check(const rtx_pass_params *pp)
 {
 	if (pp->passes < 1 || pp->passes > RTX_PASSES_MAX)
 		return fail(RTX_ERR_ARG, "%u passes outside 1..%u", pp->passes, RTX_PASSES_MAX);
@@ -54,11 +55,20 @@ static int pass_params_check(const rtx_pass_params *pp)
 	return RTX_OK;
 }
 
+/* pass k's sub-pixel offset in pixel units: what rtx_pass_frame moves the corner by, and what the reconstruction
+ * filter's weights are evaluated at (rtx_filter.cpp) */
+void rtx_pass_offset(const rtx_pass_params *pp, uint32_t k, double *ox, double *oy)
+{
+	const bool jitter = (pp->flags & RTX_PASS_JITTER) && k != 0;
+	*ox = jitter ? radical_inverse(k, 2) - 0.5 : 0.0;
+	*oy = jitter ? radical_inverse(k, 3) - 0.5 : 0.0;
+}
+
 extern "C" int rtx_pass_frame(const rtx_frame *fr, const rtx_pass_params *pp, uint32_t k, rtx_frame *out)
 {
 	if (!fr || !pp || !out)
 		return fail(RTX_ERR_ARG, "null argument");
-	int rc = pass_params_check(pp);
+	int rc = rtx_pass_params_check(pp);
 	if (rc)
 		return rc;
 	if (k >= pp->passes)
@@ -77,7 +87,8 @@ extern "C" int rtx_pass_frame(const rtx_frame *fr, const rtx_pass_params *pp, ui
 	/* the corner in double: the offset-free one keeps the input's value (and, for a pinhole, its bits) */
 	double cj[3];
 	const bool jitter = (pp->flags & RTX_PASS_JITTER) && k != 0;
-	const double ox = jitter ? radical_inverse(k, 2) - 0.5 : 0.0, oy = jitter ? radical_inverse(k, 3) - 0.5 : 0.0;
+	double ox, oy;
+	rtx_pass_offset(pp, k, &ox, &oy);
 	for (int i = 0; i < 3; i++)
 		cj[i] = jitter ? (double)fr->corner[i] + ox * sx[i] + oy * sy[i] : (double)fr->corner[i];
 	if (!lens) {
@@ -126,8 +137,8 @@ int rtx_passes_args_check(const rtx_frame *fr, const rtx_params *p, const rtx_pa
 	return RTX_OK;
 }
 
-/* everything rtx_render_passes* refuses before it launches anything */
-static int passes_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive = false)
+/* everything rtx_render_passes* refuses before it launches anything (the filtered entries too, rtx_filter.cpp) */
+int rtx_passes_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive)
 {
 	if (!c || !fr || !p || !pp)
 		return fail(RTX_ERR_ARG, "null argument");
@@ -190,7 +201,7 @@ static int passes_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, c
 extern "C" int rtx_render_passes_device(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, void *d_rgb,
 					void *d_z, void *d_variance, void *stream)
 {
-	int rc = passes_check(c, fr, p, pp);
+	int rc = rtx_passes_check(c, fr, p, pp, false);
 	if (rc)
 		return rc;
 	if (((uintptr_t)d_rgb | (uintptr_t)d_z | (uintptr_t)d_variance) & 15u)
@@ -202,7 +213,7 @@ extern "C" int rtx_render_passes_device(rtx_ctx *c, const rtx_frame *fr, const r
 extern "C" int rtx_render_passes(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, float *rgb, float *z,
 				 float *variance)
 {
-	int rc = passes_check(c, fr, p, pp);
+	int rc = rtx_passes_check(c, fr, p, pp, false);
 	if (rc)
 		return rc;
 	HIP_TRY(hipSetDevice(c->device));
@@ -226,7 +237,7 @@ extern "C" int rtx_render_passes(rtx_ctx *c, const rtx_frame *fr, const rtx_para
 /* everything rtx_render_adaptive* refuses before it launches anything */
 static int adaptive_check(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp)
 {
-	return passes_check(c, fr, p, pp, true);
+	return rtx_passes_check(c, fr, p, pp, true);
 }
 
 /* checked arguments, device outputs (each may be null) */

@@ -127,6 +127,13 @@ extern "C" RTX_HIDDEN uint32_t rtx_pass_blocks(uint64_t n)
 	return (uint32_t)(blocks < RTX_PASS_BLOCKS ? blocks : RTX_PASS_BLOCKS);
 }
 
+/* the partial sums of `blocks` blocks (2 doubles each) totalled into sums[2]; the filtered fold's too (rtx_filter.hip) */
+extern "C" RTX_HIDDEN hipError_t rtx_launch_pass_error(uint32_t blocks, const double *partials, double *sums, hipStream_t stream)
+{
+	hipLaunchKernelGGL(k_pass_error, dim3(1), dim3(64), 0, stream, blocks, partials, sums);
+	return hipGetLastError();
+}
+
 /* pass k (rgb: n pixels, packed) into state (6 n doubles).  out != 0: the mean and its variance into out_rgb /
  * out_var (each may be null), the blocks' partial sums into partials (2 * rtx_pass_blocks(n) doubles) and their
  * totals into sums[2] */
@@ -140,7 +147,7 @@ extern "C" RTX_HIDDEN hipError_t rtx_launch_pass_fold(uint64_t n, uint32_t k, in
 			hipLaunchKernelGGL((k_pass_fold<true, true>), grid, block, 0, stream, n, k, rgb, state, out_rgb, out_var, partials);
 		else
 			hipLaunchKernelGGL((k_pass_fold<false, true>), grid, block, 0, stream, n, k, rgb, state, out_rgb, out_var, partials);
-		hipLaunchKernelGGL(k_pass_error, dim3(1), dim3(64), 0, stream, blocks, partials, sums);
+		return rtx_launch_pass_error(blocks, partials, sums, stream);
 	} else if (k == 0) {
 		hipLaunchKernelGGL((k_pass_fold<true, false>), grid, block, 0, stream, n, k, rgb, state, (float *)nullptr, (float *)nullptr,
 				   (double *)nullptr);

@@ -29,6 +29,9 @@
  *   --denoise-variance   with a multi-pass flag: the render also returns the variance of the mean, and the mean
  *                goes through rtx_frame_features + rtx_denoise_variance (defaults) before it is saved (before
  *                --denoise, where both are given)
+ *   --filter box|tent|gaussian|mitchell [--filter-radius R] [--filter-alpha A]   a pixel reconstruction filter
+ *                wider than the pixel (rtx_render_passes_filtered; defaults: radius 1.5, Gaussian alpha 2); implies
+ *                --aa; composes with --lens, --target-error, --denoise and --denoise-variance, not with --adaptive
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -65,7 +68,10 @@ static const char *HELPTEXT =
 	"[--lens] (float) (float)         : DEFAULT = OFF     : thin lens: aperture radius and focus distance (16 passes unless --passes).\n"
 	"[--target-error] (float)         : DEFAULT = 0       : stop once the passes' error estimate is at most this (one GPU only).\n"
 	"[--adaptive]                     : DEFAULT = OFF     : with --target-error: a tile stops receiving passes once its share of the error is met.\n"
-	"[--denoise-variance]             : DEFAULT = OFF     : with --passes, --aa, --lens, --target-error or --adaptive: filter the mean guided by its variance.\n";
+	"[--denoise-variance]             : DEFAULT = OFF     : with --passes, --aa, --lens, --target-error or --adaptive: filter the mean guided by its variance.\n"
+	"[--filter] (box | tent | gaussian | mitchell) : DEFAULT = OFF : pixel reconstruction filter over the passes; implies --aa (not with --adaptive, one GPU only).\n"
+	"[--filter-radius] (float)        : DEFAULT = 1.5     : with --filter: the filter's radius in pixels (box 0.5..2.5, the others 1..2.5).\n"
+	"[--filter-alpha] (float)         : DEFAULT = 2       : with --filter gaussian: the falloff exp(-alpha d^2).\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -150,6 +156,49 @@ int main(int argc, char **argv)
 		pp.target_error = (float)atof(argv[idx + 1]);
 		multipass = 1;
 	}
+	/* a reconstruction filter (rtx_render_passes_filtered): the jittered passes gathered through it */
+	rtx_filter_params fp;
+	rtx_filter_params_default(&fp);
+	int filtered = 0;
+	for (int i = 1; i < argc; i++)
+		if (!strcmp(argv[i], "--filter"))
+			filtered = 1;
+	if (filtered) {
+		static const char *const kinds[] = { "box", "tent", "gaussian", "mitchell" };
+		const char *name = (idx = argv_find(argc, argv, "--filter", 1)) ? argv[idx + 1] : "";
+		uint32_t kind = 0;
+		while (kind < 4 && strcmp(name, kinds[kind]))
+			kind++;
+		if (kind == 4) {
+			LOG("--filter needs one of box, tent, gaussian, mitchell, not '%s'.", name);
+			return 1;
+		}
+		fp.kind = kind;
+		if ((idx = argv_find(argc, argv, "--filter-radius", 1)))
+			fp.radius = (float)atof(argv[idx + 1]);
+		if ((idx = argv_find(argc, argv, "--filter-alpha", 1)))
+			fp.alpha = (float)atof(argv[idx + 1]);
+		pp.flags |= RTX_PASS_JITTER;
+		if (!argv_find(argc, argv, "--passes", 1))
+			pp.passes = 16;
+		multipass = 1;
+		if (argv_find(argc, argv, "--adaptive", 0)) {
+			LOG("--filter does not combine with --adaptive: a stopped tile's neighbours have no sample to gather.");
+			return 1;
+		}
+		if (ngpu > 1) {
+			LOG("--filter renders on one GPU, not on %d.", ngpu);
+			return 1;
+		}
+		double wx[RTX_FILTER_TAPS], wy[RTX_FILTER_TAPS];
+		if (rtx_pass_filter_weights(&pp, &fp, 0, wx, wy)) {
+			LOG("%s", rtx_last_error());
+			return 1;
+		}
+	} else if (argv_find(argc, argv, "--filter-radius", 0) || argv_find(argc, argv, "--filter-alpha", 0)) {
+		LOG("--filter-radius and --filter-alpha need --filter.");
+		return 1;
+	}
 	const int adaptive = argv_find(argc, argv, "--adaptive", 0) != 0;
 	if (adaptive) {
 		if (!(pp.target_error > 0.f)) {
@@ -212,7 +261,8 @@ int main(int argc, char **argv)
 		rtx_adaptive_stats as;
 		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) ||
 		    (adaptive ? rtx_render_adaptive(ctx, &fr, &p, &pp, rgb, z, var, NULL) || rtx_get_adaptive_stats(ctx, &as)
-			      : rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, var) || rtx_get_pass_stats(ctx, &ps))) {
+		     : filtered ? rtx_render_passes_filtered(ctx, &fr, &p, &pp, &fp, rgb, z, var) || rtx_get_pass_stats(ctx, &ps)
+				: rtx_render_passes(ctx, &fr, &p, &pp, rgb, z, var) || rtx_get_pass_stats(ctx, &ps))) {
 			LOG("%s", rtx_last_error());
 			rtx_close(ctx);
 			return 1;

@@ -478,6 +478,33 @@ class Renderer:
         _check(self.lib.rtx_get_pass_stats(self._ctx, C.byref(s)))
         return s
 
+    def render_passes_filtered(self, frame, params, passes, filter="gaussian", radius=None, alpha=None, jitter=True,
+                               aperture=0.0, focus=1.0, target_error=0.0, min_passes=2):
+        """rtx_render_passes_filtered on host arrays: render_passes with every pass gathered through a pixel
+        reconstruction filter (a name of abi.FILTER_KINDS, a kind number or a FilterParams; radius / alpha None: the
+        library's defaults).  Returns (rgb, z, variance) as render_passes; pass_stats() describes the call."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        fp = _filter_of(filter, radius, alpha)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        _check(self.lib.rtx_render_passes_filtered(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), C.byref(fp),
+                                                   rgb.ctypes.data, z.ctypes.data, var.ctypes.data))
+        return rgb, z, var
+
+    def render_passes_filtered_device(self, frame, params, passes, d_rgb, d_z, d_variance, stream=None, filter="gaussian",
+                                      radius=None, alpha=None, jitter=True, aperture=0.0, focus=1.0, target_error=0.0,
+                                      min_passes=2):
+        """rtx_render_passes_filtered_device: d_rgb / d_z / d_variance are device pointers (ints, 16-byte aligned) or
+        None; stream: hipStream_t as int or None."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        fp = _filter_of(filter, radius, alpha)
+        _check(self.lib.rtx_render_passes_filtered_device(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), C.byref(fp),
+                                                          C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                                          C.c_void_p(d_variance) if d_variance else None,
+                                                          C.c_void_p(stream) if stream else None))
+
     def render_tiles(self, frame, params, tiles, rgb=None, z=None):
         """rtx_render_tiles on host arrays: the listed 8x8 tiles (row-major indices, strictly increasing) of the
         frame into rgb / z (zeros when not given); every other pixel keeps its value.  Returns (rgb, z)."""
@@ -561,6 +588,43 @@ def pass_frame(frame, k, **params):
     out = Frame()
     _check(rtx_lib().rtx_pass_frame(C.byref(frame), C.byref(pass_params(**params)), k, C.byref(out)))
     return out
+
+
+def filter_params(**params):
+    """rtx_filter_params_default plus overrides (kind: a number or a name of abi.FILTER_KINDS, radius, alpha, pad_).
+    A kind other than the default's without a radius takes radius 1.5 as well; the library checks the ranges."""
+    p = abi.FilterParams()
+    rtx_lib().rtx_filter_params_default(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        if k == "kind" and isinstance(v, str):
+            if v not in abi.FILTER_KINDS:
+                raise ValueError(f"unknown filter {v!r}: one of {sorted(abi.FILTER_KINDS)}")
+            v = abi.FILTER_KINDS[v]
+        setattr(p, k, v)
+    return p
+
+
+def _filter_of(filter, radius, alpha):
+    """a FilterParams as it is, or filter_params of a kind with the radius and alpha that are not None"""
+    if isinstance(filter, abi.FilterParams):
+        return filter
+    kw = {"kind": filter}
+    if radius is not None:
+        kw["radius"] = radius
+    if alpha is not None:
+        kw["alpha"] = alpha
+    return filter_params(**kw)
+
+
+def filter_weights(k, filter="gaussian", radius=None, alpha=None, **params):
+    """rtx_pass_filter_weights (no device needed): (wx, wy), each RTX_FILTER_TAPS float64, of pass k under
+    pass_params(**params) and the filter (as Renderer.render_passes_filtered takes it)"""
+    wx, wy = np.zeros(abi.RTX_FILTER_TAPS, np.float64), np.zeros(abi.RTX_FILTER_TAPS, np.float64)
+    fp = _filter_of(filter, radius, alpha)
+    _check(rtx_lib().rtx_pass_filter_weights(C.byref(pass_params(**params)), C.byref(fp), k, wx.ctypes.data, wy.ctypes.data))
+    return wx, wy
 
 
 def tree_frame(scene):

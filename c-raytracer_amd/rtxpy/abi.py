@@ -235,6 +235,23 @@ class GroupExchangeStats(C.Structure):
                 ("gather_ms", C.c_double)]
 
 
+# pixel reconstruction filters (rtx_pass_filter_weights, rtx_render_passes_filtered*)
+RTX_FILTER_BOX, RTX_FILTER_TENT, RTX_FILTER_GAUSSIAN, RTX_FILTER_MITCHELL = range(4)
+RTX_FILTER_TAPS = 5
+FILTER_KINDS = {"box": RTX_FILTER_BOX, "tent": RTX_FILTER_TENT, "gaussian": RTX_FILTER_GAUSSIAN,
+                "mitchell": RTX_FILTER_MITCHELL}
+# each kind's radius range in pixels
+FILTER_RADIUS = {RTX_FILTER_BOX: (0.5, 2.5), RTX_FILTER_TENT: (1.0, 2.5), RTX_FILTER_GAUSSIAN: (1.0, 2.5),
+                 RTX_FILTER_MITCHELL: (1.0, 2.5)}
+
+
+class FilterParams(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("radius", C.c_float), ("alpha", C.c_float), ("pad_", C.c_uint32)]
+
+
+# rtx_filter_params_default
+FILTER_DEFAULTS = {"kind": RTX_FILTER_GAUSSIAN, "radius": 1.5, "alpha": 2.0, "pad_": 0}
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -265,6 +282,8 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_denoise_variance_params_default", "rtx_denoise_variance_device", "rtx_denoise_variance",
                "rtx_pass_params_default", "rtx_pass_frame", "rtx_render_passes", "rtx_render_passes_device",
                "rtx_get_pass_stats",
+               "rtx_filter_params_default", "rtx_pass_filter_weights", "rtx_render_passes_filtered",
+               "rtx_render_passes_filtered_device",
                "rtx_render_tiles", "rtx_render_tiles_device",
                "rtx_render_adaptive", "rtx_render_adaptive_device", "rtx_get_adaptive_stats",
                "rtx_group_render_passes", "rtx_group_get_pass_stats", "rtx_group_render_adaptive",
@@ -455,6 +474,16 @@ def declare_rtx(lib):
     lib.rtx_render_passes_device.restype = C.c_int
     lib.rtx_get_pass_stats.argtypes = [C.c_void_p, C.POINTER(PassStats)]
     lib.rtx_get_pass_stats.restype = C.c_int
+    lib.rtx_filter_params_default.argtypes = [C.POINTER(FilterParams)]
+    lib.rtx_filter_params_default.restype = None
+    lib.rtx_pass_filter_weights.argtypes = [C.POINTER(PassParams), C.POINTER(FilterParams), C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.rtx_pass_filter_weights.restype = C.c_int
+    lib.rtx_render_passes_filtered.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams),
+                                               C.POINTER(FilterParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_passes_filtered.restype = C.c_int
+    lib.rtx_render_passes_filtered_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams),
+                                                      C.POINTER(FilterParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_passes_filtered_device.restype = C.c_int
     lib.rtx_render_tiles.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p]
     lib.rtx_render_tiles.restype = C.c_int

@@ -777,6 +777,68 @@ typedef struct rtx_pass_stats {   /* the last rtx_render_passes* of the context 
 int rtx_get_pass_stats(const rtx_ctx *ctx, rtx_pass_stats *out);
 
 /*
+ * Pixel reconstruction filters for multi-pass rendering.  rtx_render_passes gives a pass's sample
+ * to one pixel, a box one pixel wide; the filtered entries give it to every pixel whose filter footprint holds it.
+ * In pass k pixel q = (qx, qy) is sampled at q + (ox_k, oy_k) in pixel-index units, (ox_k, oy_k) rtx_pass_frame's
+ * offset, each in the open interval (-1/2, 1/2).  The filter is separable, w(dx, dy) = f(dx) f(dy), of radius r
+ * pixels:
+ *   RTX_FILTER_BOX       f(d) = 1 if -r <= d < r, else 0                                   r in 0.5 .. 2.5
+ *   RTX_FILTER_TENT      f(d) = max(0, 1 - |d| / r)                                        r in 1 .. 2.5
+ *   RTX_FILTER_GAUSSIAN  f(d) = exp(-alpha d^2) - exp(-alpha r^2) if |d| < r, else 0       r in 1 .. 2.5,
+ *                        alpha > 0 and finite (the default: r = 1.5, alpha = 2)
+ *   RTX_FILTER_MITCHELL  f(d) = m(|2 d / r|) if |d| < r, else 0, m the Mitchell-Netravali   r in 1 .. 2.5
+ *                        cubic with B = C = 1/3, evaluated by Horner's rule as
+ *                        m(x) = ((7 x - 12) x x + 16/3) / 6 for x < 1, else (((-7/3 x + 12) x - 20) x + 32/3) / 6
+ * all in double from the float parameters.  With r <= 2.5 only the taps dq in -2 .. 2 per axis can carry weight:
+ * the stencil is always RTX_FILTER_TAPS x RTX_FILTER_TAPS.  For pass k the host evaluates wx[i] = f(i - 2 + ox_k),
+ * wy[j] = f(j - 2 + oy_k); a tap's weight is the double product wx[i] wy[j].
+ *
+ * For output pixel p and pass k, over the taps q = p + (i - 2, j - 2) that lie inside the frame and whose weight
+ * is not 0 (a zero-weight tap is skipped, not multiplied: a non-finite neighbour outside the footprint does not
+ * reach p), in row-major tap order (j outer, i inner), per channel and in double:
+ *   S_k = sum w c_k(q),  W_k = sum w,  f_k = S_k / W_k
+ * and the fold, per channel, on double state (mean, M2, and Wsum per pixel):
+ *   k = 0:  mean = f_0, M2 = 0, Wsum = W_0
+ *   k > 0:  Wsum += W_k;  d = f_k - mean;  mean += (d W_k) / Wsum;  M2 += (W_k d) (f_k - mean)
+ *   rgb = (float)mean,  variance = (float)(M2 / (Wsum (n - 1))), n = k + 1 passes (0 for n = 1),  z = pass 0's z
+ * With equal weights this is rtx_render_passes's update; with RTX_FILTER_BOX of radius 0.5 every pass has the one
+ * tap q = p of weight 1, and rgb, variance and z are rtx_render_passes's bit for bit.  W_k > 0 always: the tap
+ * q = p lies in the frame and has a positive weight under box, tent and Gaussian, and Mitchell's per-axis weight
+ * sum stays above 0.05 under every truncation by the frame's border over its radius range.  A non-finite tap of
+ * non-zero weight makes p non-finite from then on (as a non-finite pass value does in rtx_render_passes).
+ * The error, the stopping rule and rtx_pass_stats are rtx_render_passes's, on the filtered mean and variance; the
+ * error's partial sums are per 32x8-pixel tile, so it differs from rtx_render_passes's by double rounding.
+ * A filter without RTX_PASS_JITTER is allowed: a plain blur with the weights at integer offsets.
+ * Not filtered: rtx_render_adaptive* and the device group's entries (a stopped or foreign tile's neighbours have
+ * no sample to gather).
+ */
+enum { RTX_FILTER_BOX = 0, RTX_FILTER_TENT = 1, RTX_FILTER_GAUSSIAN = 2, RTX_FILTER_MITCHELL = 3 };
+#define RTX_FILTER_TAPS 5
+typedef struct rtx_filter_params {
+	uint32_t kind;          /* RTX_FILTER_* */
+	float radius;           /* in pixels, within the kind's range above */
+	float alpha;            /* RTX_FILTER_GAUSSIAN's falloff; ignored by the other kinds */
+	uint32_t pad_;          /* 0 */
+} rtx_filter_params;
+void rtx_filter_params_default(rtx_filter_params *p);   /* Gaussian, radius 1.5, alpha 2 */
+/* The two weight tables of pass k (host only, no device needed).  RTX_ERR_ARG: a null pointer, every rtx_pass_frame
+ * error about pp and k, an unknown kind, a radius outside the kind's range or NaN, a Gaussian alpha <= 0 or not
+ * finite, a non-zero pad_. */
+int rtx_pass_filter_weights(const rtx_pass_params *pp, const rtx_filter_params *fp, uint32_t k, double wx[RTX_FILTER_TAPS],
+			    double wy[RTX_FILTER_TAPS]);
+/* rtx_render_passes with the reconstruction filter fp.  HOST buffers; each may be NULL.  Errors: everything
+ * rtx_render_passes refuses, with its codes; RTX_ERR_ARG for a null fp, every rtx_pass_filter_weights error about
+ * fp, and a frame of more than 2^24 tiles of 32x8 pixels.  A refused call leaves the context and its statistics as
+ * they were.  rtx_get_pass_stats afterwards describes this call (accum_ms: the filtered fold's). */
+int rtx_render_passes_filtered(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			       const rtx_filter_params *fp, float *rgb, float *z, float *variance);
+/* Same into DEVICE buffers (16-byte aligned, each may be NULL), enqueued on `stream` (NULL = the context's
+ * own); synchronises the stream. */
+int rtx_render_passes_filtered_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params,
+				      const rtx_pass_params *pp, const rtx_filter_params *fp, void *d_rgb, void *d_z,
+				      void *d_variance, void *stream);
+
+/*
  * Tile-list renders: exactly the tiles the caller names, each bit for bit the tile rtx_render gives for the whole
  * frame (a pixel's random numbers are keyed on the seed and the pixel, and a tile's pixels do not depend on which
  * other tiles are rendered with it).  tiles[i] is a row-major index of an 8x8-pixel tile (tile t covers columns
