@@ -72,8 +72,9 @@ static int features_check(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, cons
 	return RTX_OK;
 }
 
-/* checked arguments, d_features on the device: the frame's rays, their closest hits, the records */
-static int features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, hipStream_t stream)
+/* checked arguments, d_features on the device: the frame's rays, their closest hits, the records (the upsampling
+ * pipeline's two feature calls too, rtx_upsample.cpp) */
+int rtx_features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, hipStream_t stream)
 {
 	if ((uintptr_t)d_features & 15u)
 		return fail(RTX_ERR_ARG, "feature buffer must be 16-byte aligned");
@@ -108,7 +109,7 @@ extern "C" int rtx_frame_features_device(rtx_ctx *c, const rtx_frame *fr, int32_
 	if (rc)
 		return rc;
 	HIP_TRY(hipSetDevice(c->device));
-	return features_common(c, fr, u32conv, d_features, stream ? (hipStream_t)stream : c->stream);
+	return rtx_features_common(c, fr, u32conv, d_features, stream ? (hipStream_t)stream : c->stream);
 }
 
 extern "C" int rtx_frame_features(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, rtx_feature *features)
@@ -120,7 +121,7 @@ extern "C" int rtx_frame_features(rtx_ctx *c, const rtx_frame *fr, int32_t u32co
 	const size_t bytes = (size_t)fr->width * fr->height * sizeof(rtx_feature);
 	if (c->d_dn_feat.grow(bytes) != hipSuccess)
 		return fail(RTX_ERR_NOMEM, "device copy of %zu B of features", bytes);
-	rc = features_common(c, fr, u32conv, c->d_dn_feat, c->stream);
+	rc = rtx_features_common(c, fr, u32conv, c->d_dn_feat, c->stream);
 	if (rc)
 		return rc;
 	HIP_TRY(hipMemcpy(features, c->d_dn_feat, bytes, hipMemcpyDeviceToHost));

@@ -2,7 +2,7 @@
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
  * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
- * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
+ * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_upsample.cpp (feature-guided upsampling), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
@@ -231,6 +231,14 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float> d_ad_var;       /* the host-buffer call's device copies */
 	DevBuf<uint32_t> d_ad_passes;
 	rtx_adaptive_stats ad_stats{};
+	/* feature-guided upsampling (rtx_upsample*, rtx_render_upsampled*): grow-only scratch of its own, rtx_upsample.hip */
+	DevBuf<float> d_up_low_rgb;       /* the low frame: the pipeline's render, the host-buffer call's device copy */
+	DevBuf<float4> d_up_low_feat, d_up_feat; /* the records of the low and of the full frame, likewise */
+	DevBuf<float> d_up_rgb, d_up_conf;
+	DevBuf<uint32_t> d_up_count;      /* pixels below the threshold per tile */
+	DevBuf<uint32_t> d_up_list;       /* the refinement list */
+	DevBuf<unsigned long long> d_up_out; /* its length, and the pixels below the threshold */
+	rtx_upsample_stats up_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;
@@ -340,6 +348,10 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 RTX_HIDDEN void rtx_free_scene(rtx_ctx *c);
 /* rtx_query.cpp: n checked rays on device buffers into c->ray_stats (the feature buffers' query too) */
 RTX_HIDDEN int rtx_rays_common(rtx_ctx *c, uint32_t n, const void *d_rays, void *d_hits, uint32_t flags, hipStream_t stream);
+
+/* rtx_image.cpp: the feature records of a checked frame into a 16-byte aligned device buffer, on stream (synchronised);
+ * fills c->dn_stats as rtx_frame_features_device does (the upsampling pipeline's two feature calls, rtx_upsample.cpp) */
+RTX_HIDDEN int rtx_features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, hipStream_t stream);
 
 /* rtx_passes.cpp: what the multi-pass (adaptive: and the adaptive) entries refuse about non-null arguments */
 RTX_HIDDEN int rtx_passes_args_check(const rtx_frame *fr, const rtx_params *p, const rtx_pass_params *pp, bool adaptive);

@@ -160,6 +160,14 @@ RTX_HIDDEN hipError_t rtx_launch_tile_out(uint32_t w, uint32_t h, const double *
 					  float *var, uint32_t *tile_passes, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_adaptive(void);
 
+/* rtx_upsample.hip: the feature-guided upsampler, the z copy and the refinement list of rtx_render_upsampled* */
+RTX_HIDDEN hipError_t rtx_launch_upsample(uint32_t w, uint32_t h, const rtx_upsample_params *up, const float *low_rgb,
+					  const float4 *low_feat, const float4 *feat, float *rgb, float *conf, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_upsample_z(uint64_t n, const float4 *feat, float *z, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_launch_upsample_tiles(uint32_t w, uint32_t h, float threshold, const float *conf, uint32_t *count,
+						uint32_t *list, unsigned long long *out, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_upsample(void);
+
 }
 
 #endif

@@ -32,6 +32,10 @@
  *   --filter box|tent|gaussian|mitchell [--filter-radius R] [--filter-alpha A]   a pixel reconstruction filter
  *                wider than the pixel (rtx_render_passes_filtered; defaults: radius 1.5, Gaussian alpha 2); implies
  *                --aa; composes with --lens, --target-error, --denoise and --denoise-variance, not with --adaptive
+ *   --upsample S [--refine T]   the frame rendered at 1/S of the resolution per axis (S in 1..8), upsampled under the
+ *                guidance of the full-resolution feature records, and the 8x8 tiles that hold a pixel of confidence
+ *                below T (default 0.5) re-rendered at full resolution (rtx_render_upsampled).  One GPU; implies
+ *                nothing else, composes with --denoise, not with the multi-pass flags
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,7 +75,9 @@ static const char *HELPTEXT =
 	"[--denoise-variance]             : DEFAULT = OFF     : with --passes, --aa, --lens, --target-error or --adaptive: filter the mean guided by its variance.\n"
 	"[--filter] (box | tent | gaussian | mitchell) : DEFAULT = OFF : pixel reconstruction filter over the passes; implies --aa (not with --adaptive, one GPU only).\n"
 	"[--filter-radius] (float)        : DEFAULT = 1.5     : with --filter: the filter's radius in pixels (box 0.5..2.5, the others 1..2.5).\n"
-	"[--filter-alpha] (float)         : DEFAULT = 2       : with --filter gaussian: the falloff exp(-alpha d^2).\n";
+	"[--filter-alpha] (float)         : DEFAULT = 2       : with --filter gaussian: the falloff exp(-alpha d^2).\n"
+	"[--upsample] (integer)           : DEFAULT = OFF     : render at 1/S of the resolution per axis (S in 1..8), upsample guided by the full-resolution features, refine the uncertain tiles (one GPU only, not with the multi-pass flags).\n"
+	"[--refine] (float)               : DEFAULT = 0.5     : with --upsample: re-render at full resolution the 8x8 tiles that hold a pixel of confidence below this.\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -218,6 +224,35 @@ int main(int argc, char **argv)
 		LOG("--passes, --aa, --lens, --target-error and --adaptive render on one GPU, not on %d.", ngpu);
 		return 1;
 	}
+	/* feature-guided upsampling (rtx_render_upsampled): a low-resolution render, refined where it is uncertain */
+	rtx_upsample_params up;
+	rtx_upsample_params_default(&up);
+	int upsample = 0;
+	for (int i = 1; i < argc; i++)
+		if (!strcmp(argv[i], "--upsample"))
+			upsample = 1;
+	if (upsample) {
+		const long S = (idx = argv_find(argc, argv, "--upsample", 1)) ? strtol(argv[idx + 1], NULL, 10) : 0;
+		if (S < 1 || S > (long)RTX_UPSAMPLE_SCALE_MAX) {
+			LOG("--upsample needs a scale in 1..%u.", RTX_UPSAMPLE_SCALE_MAX);
+			return 1;
+		}
+		up.scale = (uint32_t)S;
+		if ((idx = argv_find(argc, argv, "--refine", 1)))
+			up.refine_threshold = (float)atof(argv[idx + 1]);
+		if (ngpu > 1) {
+			LOG("--upsample renders on one GPU, not on %d.", ngpu);
+			return 1;
+		}
+		if (multipass || denoise_variance) {
+			LOG("--upsample does not combine with --passes, --aa, --lens, --filter, --adaptive, --target-error or "
+			    "--denoise-variance: render the scaled frame (rtx_frame_scaled) through the library instead.");
+			return 1;
+		}
+	} else if (argv_find(argc, argv, "--refine", 0)) {
+		LOG("--refine needs --upsample.");
+		return 1;
+	}
 
 	LOG("Loading scene.");
 	const char *scale = NULL;
@@ -283,6 +318,24 @@ int main(int argc, char **argv)
 			shadow = ps.shadow_rays;
 			kms = ps.render_ms;
 		}
+	} else if (upsample) {
+		rtx_ctx *ctx = NULL;
+		rtx_upsample_stats us;
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_render_upsampled(ctx, &fr, &p, &up, rgb, z) ||
+		    rtx_get_upsample_stats(ctx, &us)) {
+			LOG("%s", rtx_last_error());
+			rtx_close(ctx);
+			return 1;
+		}
+		rtx_close(ctx);
+		LOG("Upsampled %ux%u by %u: %u of %u tiles refined (%.1f %%), %llu pixels below confidence %g; low render %.3f ms, "
+		    "features %.3f ms, upsample %.3f ms, refinement %.3f ms.",
+		    us.low_width, us.low_height, up.scale, us.refined_tiles, us.tiles, us.tiles ? 100.0 * us.refined_tiles / us.tiles : 0.0,
+		    (unsigned long long)us.low_conf_pixels, (double)up.refine_threshold, us.low_ms, us.features_ms, us.upsample_ms,
+		    us.refine_ms);
+		closest = us.closest_rays;
+		shadow = us.shadow_rays;
+		kms = us.low_ms + us.features_ms + us.upsample_ms + us.refine_ms;
 	} else {
 		rtx_group *grp = NULL;
 		if (rtx_group_open(ngpu, devs, &grp) || rtx_group_upload_scene(grp, desc) ||

@@ -557,6 +557,72 @@ class Renderer:
         _check(self.lib.rtx_get_adaptive_stats(self._ctx, C.byref(s)))
         return s
 
+    def upsample(self, low_rgb, low_features, features, conf=True, **params):
+        """rtx_upsample on host arrays: low_rgb (lh, lw, 3) float32 and low_features (lh, lw) of the low frame,
+        features (h, w) of the full frame, with lw = ceil(w / scale) and lh = ceil(h / scale).  Returns (rgb (h, w, 3),
+        conf (h, w)); conf=False passes no confidence buffer and returns (rgb, None)."""
+        low = np.ascontiguousarray(low_rgb, dtype=np.float32)
+        lf = np.ascontiguousarray(low_features, dtype=abi.FEATURE_DTYPE)
+        feat = np.ascontiguousarray(features, dtype=abi.FEATURE_DTYPE)
+        p = upsample_params(**params)
+        h, w = feat.shape
+        s = int(p.scale)
+        if 1 <= s <= abi.RTX_UPSAMPLE_SCALE_MAX and (lf.shape != (-(-h // s), -(-w // s)) or low.shape != lf.shape + (3,)):
+            raise ValueError("the low frame is not ceil(w / scale) x ceil(h / scale)")  # another scale: the library refuses
+        rgb = np.zeros((h, w, 3), np.float32)
+        cf = np.zeros((h, w), np.float32) if conf else None
+        _check(self.lib.rtx_upsample(self._ctx, w, h, C.byref(p), low.ctypes.data, lf.ctypes.data, feat.ctypes.data,
+                                     rgb.ctypes.data, cf.ctypes.data if conf else None))
+        return rgb, cf
+
+    def upsample_device(self, width, height, d_low_rgb, d_low_features, d_features, d_rgb, d_conf, stream=None, **params):
+        """rtx_upsample_device: device pointers (ints; the feature buffers 16-byte aligned), d_conf may be None;
+        stream: hipStream_t as int or None."""
+        p = upsample_params(**params)
+        _check(self.lib.rtx_upsample_device(self._ctx, width, height, C.byref(p), C.c_void_p(d_low_rgb),
+                                            C.c_void_p(d_low_features), C.c_void_p(d_features), C.c_void_p(d_rgb),
+                                            C.c_void_p(d_conf) if d_conf else None, C.c_void_p(stream) if stream else None))
+
+    def upsample_tiles(self, conf, threshold):
+        """rtx_upsample_tiles on a host array: the increasing row-major indices (uint32) of the 8x8 tiles of the (h, w)
+        confidence buffer that hold a pixel with conf < threshold, as render_tiles takes them."""
+        cf = np.ascontiguousarray(conf, dtype=np.float32)
+        h, w = cf.shape
+        tiles = np.zeros(((h + 7) // 8) * ((w + 7) // 8), np.uint32)
+        n = C.c_uint32(0)
+        _check(self.lib.rtx_upsample_tiles(self._ctx, w, h, cf.ctypes.data, float(threshold), tiles.ctypes.data, C.byref(n)))
+        return tiles[:n.value].copy()
+
+    def upsample_tiles_device(self, width, height, d_conf, threshold, d_tiles, stream=None):
+        """rtx_upsample_tiles_device: d_conf / d_tiles are device pointers (ints); returns the list's length."""
+        n = C.c_uint32(0)
+        _check(self.lib.rtx_upsample_tiles_device(self._ctx, width, height, C.c_void_p(d_conf), float(threshold),
+                                                  C.c_void_p(d_tiles), C.byref(n), C.c_void_p(stream) if stream else None))
+        return n.value
+
+    def render_upsampled(self, frame, params, **up):
+        """rtx_render_upsampled on host arrays: the frame rendered at 1 / scale of the resolution, upsampled under the
+        guidance of the full frame's features, and the tiles of confidence below refine_threshold re-rendered at full
+        resolution.  Returns (rgb (h, w, 3), z (h, w)); upsample_stats() tells what was refined."""
+        p = upsample_params(**up)
+        w, h = frame.width, frame.height
+        rgb, z = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        _check(self.lib.rtx_render_upsampled(self._ctx, C.byref(frame), C.byref(params), C.byref(p), rgb.ctypes.data,
+                                             z.ctypes.data))
+        return rgb, z
+
+    def render_upsampled_device(self, frame, params, d_rgb, d_z, stream=None, **up):
+        """rtx_render_upsampled_device: d_rgb / d_z are device pointers (ints, 16-byte aligned) or None."""
+        p = upsample_params(**up)
+        _check(self.lib.rtx_render_upsampled_device(self._ctx, C.byref(frame), C.byref(params), C.byref(p),
+                                                    C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                                    C.c_void_p(stream) if stream else None))
+
+    def upsample_stats(self):
+        s = abi.UpsampleStats()
+        _check(self.lib.rtx_get_upsample_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)
@@ -587,6 +653,26 @@ def pass_frame(frame, k, **params):
     """rtx_pass_frame (no device needed): the frame of pass k of `frame` under pass_params(**params)"""
     out = Frame()
     _check(rtx_lib().rtx_pass_frame(C.byref(frame), C.byref(pass_params(**params)), k, C.byref(out)))
+    return out
+
+
+def upsample_params(**params):
+    """rtx_upsample_params_default plus overrides (scale, match_material, demodulate, sigma_normal / _albedo / _plane,
+    albedo_min, refine_threshold)"""
+    p = abi.UpsampleParams()
+    rtx_lib().rtx_upsample_params_default(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def frame_scaled(frame, scale):
+    """rtx_frame_scaled (no device needed): the frame of 1 / scale of the resolution per axis whose pixel (c, r) looks
+    through the centre of the scale x scale block of `frame`'s pixels it stands for"""
+    out = Frame()
+    _check(rtx_lib().rtx_frame_scaled(C.byref(frame), scale, C.byref(out)))
     return out
 
 

@@ -252,6 +252,28 @@ class FilterParams(C.Structure):
 # rtx_filter_params_default
 FILTER_DEFAULTS = {"kind": RTX_FILTER_GAUSSIAN, "radius": 1.5, "alpha": 2.0, "pad_": 0}
 
+# feature-guided upsampling (rtx_frame_scaled, rtx_upsample*, rtx_upsample_tiles*, rtx_render_upsampled*)
+RTX_UPSAMPLE_SCALE_MAX = 8
+RTX_UPSAMPLE_E_MAX = 32.0
+
+
+class UpsampleParams(C.Structure):
+    _fields_ = [("scale", C.c_uint32), ("match_material", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_plane", C.c_float),
+                ("albedo_min", C.c_float), ("refine_threshold", C.c_float)]
+
+
+class UpsampleStats(C.Structure):
+    _fields_ = [("low_width", C.c_uint32), ("low_height", C.c_uint32), ("tiles", C.c_uint32), ("refined_tiles", C.c_uint32),
+                ("low_conf_pixels", C.c_uint64), ("low_ms", C.c_double), ("features_ms", C.c_double),
+                ("upsample_ms", C.c_double), ("refine_ms", C.c_double), ("closest_rays", C.c_uint64),
+                ("shadow_rays", C.c_uint64)]
+
+
+# rtx_upsample_params_default
+UPSAMPLE_DEFAULTS = {"scale": 2, "match_material": 1, "demodulate": 0, "sigma_normal": 0.05, "sigma_albedo": 0.1,
+                     "sigma_plane": 0.02, "albedo_min": 1.0 / 64.0, "refine_threshold": 0.5}
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -288,7 +310,10 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_render_adaptive", "rtx_render_adaptive_device", "rtx_get_adaptive_stats",
                "rtx_group_render_passes", "rtx_group_get_pass_stats", "rtx_group_render_adaptive",
                "rtx_group_get_adaptive_stats", "rtx_group_get_exchange_stats",
-               "rtx_pass_pack_host", "rtx_pass_unpack_host", "rtx_pass_pack_device", "rtx_pass_unpack_device"]
+               "rtx_pass_pack_host", "rtx_pass_unpack_host", "rtx_pass_pack_device", "rtx_pass_unpack_device",
+               "rtx_upsample_params_default", "rtx_frame_scaled", "rtx_upsample", "rtx_upsample_device",
+               "rtx_upsample_tiles", "rtx_upsample_tiles_device", "rtx_render_upsampled", "rtx_render_upsampled_device",
+               "rtx_get_upsample_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -522,6 +547,30 @@ def declare_rtx(lib):
     lib.rtx_pass_unpack_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rtx_pass_unpack_device.restype = C.c_int
+    lib.rtx_upsample_params_default.argtypes = [C.POINTER(UpsampleParams)]
+    lib.rtx_upsample_params_default.restype = None
+    lib.rtx_frame_scaled.argtypes = [C.POINTER(Frame), C.c_uint32, C.POINTER(Frame)]
+    lib.rtx_frame_scaled.restype = C.c_int
+    lib.rtx_upsample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
+    lib.rtx_upsample.restype = C.c_int
+    lib.rtx_upsample_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_upsample_device.restype = C.c_int
+    lib.rtx_upsample_tiles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p,
+                                       C.POINTER(C.c_uint32)]
+    lib.rtx_upsample_tiles.restype = C.c_int
+    lib.rtx_upsample_tiles_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p,
+                                              C.POINTER(C.c_uint32), C.c_void_p]
+    lib.rtx_upsample_tiles_device.restype = C.c_int
+    lib.rtx_render_upsampled.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(UpsampleParams), C.c_void_p,
+                                         C.c_void_p]
+    lib.rtx_render_upsampled.restype = C.c_int
+    lib.rtx_render_upsampled_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(UpsampleParams),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_upsampled_device.restype = C.c_int
+    lib.rtx_get_upsample_stats.argtypes = [C.c_void_p, C.POINTER(UpsampleStats)]
+    lib.rtx_get_upsample_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

@@ -955,6 +955,111 @@ int rtx_pass_unpack_device(rtx_ctx *ctx, const void *d_in, uint32_t width, uint3
 			   uint32_t stride, void *d_rgb, void *d_z, void *d_variance, void *stream);
 
 /*
+ * Feature-guided upsampling with full-resolution tile refinement: the frame rendered at 1/s of the
+ * resolution per axis, reconstructed at full resolution by a joint-bilateral upsampler guided by the full-resolution
+ * feature records, and the 8x8 tiles in which the low frame has no usable sample re-rendered at full resolution.
+ *
+ * The low frame.  rtx_frame_scaled (host only, no device needed): out->width = ceil(W / s), out->height =
+ * ceil(H / s), step_x and step_y multiplied by s, the origin kept, and
+ *     corner_low = corner + ((1 - s) / 2) step_x + ((s - 1) / 2) step_y
+ * every component in double from the float fields, rounded to float once.  The renderer forms pixel (col, row)'s
+ * plane point as corner + row step_y + (col + 1) step_x (render.c:353-363), so low pixel (c, r) looks through the
+ * centre of the s x s block of full pixels (c s .., r s ..) it stands for, the blocks the frame's border cuts off
+ * included.  s = 1 returns *frame bit for bit.  The result is an ordinary rtx_frame: every render entry renders it.
+ * Full pixel (X, Y) sits at the low coordinates u = (X - (s - 1) / 2) / s, v = (Y - (s - 1) / 2) / s.
+ * RTX_ERR_ARG: a null pointer, s outside 1..RTX_UPSAMPLE_SCALE_MAX, an empty frame.
+ *
+ * The upsampler.  For full pixel p = (X, Y): x0 = floor(u), fx = u - x0 (exactly: with n = 2 X - (s - 1), x0 =
+ * floor(n / 2 s) and fx = (n - 2 s x0) / 2 s), likewise y0 and fy.  The taps are the four low pixels q = (x0 + i,
+ * y0 + j), i, j in {0, 1}, of bilinear weight b = (i ? fx : 1 - fx) (j ? fy : 1 - fy).  Only the taps inside the low
+ * frame with b > 0 are considered (a zero-weight tap is skipped, not multiplied); at least one always remains.
+ * With f_p the full frame's record of p, f_q the low frame's record of q and c_q the low frame's colour, a tap is
+ * usable iff c_q is finite and q is of p's kind:
+ *     both are misses (z == 0):                                                              g = 1
+ *     both are hits and (match_material == 0 or material_p == material_q):
+ *         e = |n_p - n_q|^2 / sigma_normal^2 + |a_p - a_q|^2 / sigma_albedo^2
+ *           + (n_p . (P_q - P_p))^2 / (sigma_plane z_p)^2,                                   g = exp(-e)
+ *         where e > RTX_UPSAMPLE_E_MAX or e is NaN (0 * inf) the tap is not usable
+ * and every other tap has g = 0.  Over the considered taps in row-major order (j outer, i inner):
+ *     out  = sum b g (m o c_q) / sum b g        m = 1, or with demodulate per channel a_p / a_q where both are
+ *                                               >= albedo_min and 1 otherwise
+ *     conf = sum b g / sum b                    (the denominator over ALL considered taps: an unusable one lowers it)
+ * Where sum b g == 0: out = sum b c_q / sum b over the considered taps with a finite colour (0 if there is none) and
+ * conf = 0.  The cut at RTX_UPSAMPLE_E_MAX (exp(-32) = 1.3e-14) keeps every weight a normal float whose relative
+ * error is bounded; a pixel whose every tap lies beyond it has no usable sample and is better refined than averaged.
+ * With s = 1 and the same records on both sides every pixel has its one tap of weight 1 with e = 0: out is the
+ * input's bits (a finite colour) and conf is 1, with or without demodulate.  One pixel per lane, no atomics: two
+ * runs give the same bits.  Needs no uploaded scene (like rtx_denoise).
+ */
+#define RTX_UPSAMPLE_SCALE_MAX 8u
+#define RTX_UPSAMPLE_E_MAX 32.f
+typedef struct rtx_upsample_params {
+	uint32_t scale;            /* 1..RTX_UPSAMPLE_SCALE_MAX, default 2 */
+	int32_t match_material;    /* default 1: a tap of another material is rejected */
+	int32_t demodulate;        /* default 0 */
+	float sigma_normal, sigma_albedo, sigma_plane;   /* each > 0; INFINITY switches its term off.  Defaults 0.05 / 0.1 /
+	                            * 0.02 (rtx_denoise's) */
+	float albedo_min;          /* > 0, default 1/64: below it a channel is not demodulated */
+	float refine_threshold;    /* default 0.5; read by rtx_render_upsampled* only */
+} rtx_upsample_params;
+void rtx_upsample_params_default(rtx_upsample_params *p);
+int rtx_frame_scaled(const rtx_frame *frame, uint32_t scale, rtx_frame *out);
+/* HOST buffers: low_rgb 3 floats and low_features one record per pixel of the ceil(w / s) x ceil(h / s) low frame,
+ * features one record per pixel of the w x h full frame; rgb[w*h*3] and conf[w*h] are written (conf may be NULL).
+ * RTX_ERR_ARG before anything is launched: a null context, params or buffer (conf excepted), a scale outside
+ * 1..RTX_UPSAMPLE_SCALE_MAX, a sigma or albedo_min that is <= 0 or NaN, w * h == 0 or above RTX_RAYS_MAX. */
+int rtx_upsample(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_upsample_params *params, const float *low_rgb,
+		 const rtx_feature *low_features, const rtx_feature *features, float *rgb, float *conf);
+/* Same on DEVICE buffers (both feature buffers 16-byte aligned, RTX_ERR_ARG otherwise; the others 4-byte aligned),
+ * enqueued on `stream` (NULL = the context's own); synchronises it. */
+int rtx_upsample_device(rtx_ctx *ctx, uint32_t w, uint32_t h, const rtx_upsample_params *params, const void *d_low_rgb,
+			const void *d_low_features, const void *d_features, void *d_rgb, void *d_conf, void *stream);
+/*
+ * The refinement list: the row-major indices of the 8x8 tiles of a w x h frame that hold at least one pixel with
+ * conf < threshold (a float compare: a NaN is not below), strictly increasing, which is what rtx_render_tiles
+ * accepts; *n_tiles their number.  tiles has room for ceil(w / 8) * ceil(h / 8) entries; entries past *n_tiles are
+ * not written.  A per-tile count and an ordered compaction (ballot prefix per wave, the waves' counts added in
+ * order), no atomics: the same input gives the same list.  Every conf the upsampler writes lies in 0..1, so a
+ * threshold <= 0 gives an empty list and one > 1 every tile.  RTX_ERR_ARG: a null argument, w * h == 0 or above RTX_RAYS_MAX,
+ * more than 2^26 tiles.  Fills tiles, refined_tiles and low_conf_pixels of rtx_upsample_stats.
+ */
+int rtx_upsample_tiles(rtx_ctx *ctx, uint32_t w, uint32_t h, const float *conf, float threshold, uint32_t *tiles,
+		       uint32_t *n_tiles);
+/* Same with DEVICE conf and tiles (4-byte aligned); n_tiles is a HOST pointer (the call synchronises the stream). */
+int rtx_upsample_tiles_device(rtx_ctx *ctx, uint32_t w, uint32_t h, const void *d_conf, float threshold, void *d_tiles,
+			      uint32_t *n_tiles, void *stream);
+/*
+ * The whole pipeline: rtx_frame_scaled(frame, up->scale); rtx_render of the low frame with params as given; the
+ * feature records of both frames with params->u32conv; the upsample into rgb; z from the full frame's records
+ * (rtx_render's z buffer bit for bit); the tile list at up->refine_threshold; rtx_render_tiles of the full frame
+ * over that list with the same params.  Every refined tile is bit for bit the tile rtx_render(frame, params) gives;
+ * a threshold > 1 returns rtx_render's rgb and z bit for bit; a threshold <= 0 renders no full-resolution pixel.
+ * HOST buffers rgb[W*H*3] and z[W*H]; either may be NULL.
+ * RTX_ERR_ARG: a null context, frame, params or up, an empty frame, params->tile_offset / tile_stride other than
+ * 0 / 1, and what rtx_upsample refuses about up; RTX_ERR_STATE before an upload; otherwise the errors of rtx_render.
+ * All raised before anything is launched.  rtx_get_stats afterwards describes the last render the call made (the
+ * refinement, or the low render when no tile was refined); rtx_get_denoise_stats the full frame's feature call.
+ */
+int rtx_render_upsampled(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_upsample_params *up,
+			 float *rgb, float *z);
+/* Same into DEVICE buffers (16-byte aligned, either may be NULL), enqueued on `stream` (NULL = the context's own);
+ * synchronises the stream. */
+int rtx_render_upsampled_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params,
+				const rtx_upsample_params *up, void *d_rgb, void *d_z, void *stream);
+typedef struct rtx_upsample_stats {   /* the last rtx_upsample*, rtx_upsample_tiles* or rtx_render_upsampled* of the context */
+	uint32_t low_width, low_height;  /* the low frame (rtx_upsample*, rtx_render_upsampled*) */
+	uint32_t tiles, refined_tiles;   /* T, and the tiles listed (rtx_upsample_tiles*, rtx_render_upsampled*) */
+	uint64_t low_conf_pixels;        /* pixels with conf < threshold */
+	double low_ms;                   /* rtx_render_upsampled*: the low render's rtx_stats.kernel_ms */
+	double features_ms;              /* ... both feature calls, HIP events */
+	double upsample_ms;              /* the upsample kernel (rtx_upsample*), the list kernels (rtx_upsample_tiles*), or
+	                                  * both and the z copy (rtx_render_upsampled*), HIP events */
+	double refine_ms;                /* rtx_render_upsampled*: the refinement's rtx_stats.kernel_ms (0: no tile) */
+	uint64_t closest_rays, shadow_rays;   /* rtx_render_upsampled*: summed over both renders */
+} rtx_upsample_stats;
+int rtx_get_upsample_stats(const rtx_ctx *ctx, rtx_upsample_stats *out);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
