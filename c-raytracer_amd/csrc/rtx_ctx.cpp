@@ -232,6 +232,11 @@ extern "C" int rtx_set_option(rtx_ctx *c, int option, int64_t value)
 			return fail(RTX_ERR_ARG, "shadow specular shortcut %lld is not 0 or 1", (long long)value);
 		c->opt_spec = (int)value;
 		return RTX_OK;
+	case RTX_OPT_SHADOW_CLEARLANE:
+		if (value < 0 || value > 1)
+			return fail(RTX_ERR_ARG, "shadow clear lanes %lld is not 0 or 1", (long long)value);
+		c->opt_clearlane = (int)value;
+		return RTX_OK;
 	case RTX_OPT_SHADOW_PREMASK:
 		if (value < 0 || value > 1)
 			return fail(RTX_ERR_ARG, "shadow pre-mask %lld is not 0 or 1", (long long)value);
@@ -306,6 +311,7 @@ extern "C" int rtx_get_point_stats(const rtx_ctx *c, rtx_point_stats *out) { ret
 extern "C" int rtx_get_dark_stats(const rtx_ctx *c, rtx_dark_stats *out) { return get_stats(c, &rtx_ctx::dstats, out); }
 extern "C" int rtx_get_order_stats(const rtx_ctx *c, rtx_order_stats *out) { return get_stats(c, &rtx_ctx::ostats, out); }
 extern "C" int rtx_get_premask_stats(const rtx_ctx *c, rtx_premask_stats *out) { return get_stats(c, &rtx_ctx::mstats, out); }
+extern "C" int rtx_get_clearlane_stats(const rtx_ctx *c, rtx_clearlane_stats *out) { return get_stats(c, &rtx_ctx::cstats, out); }
 extern "C" int rtx_get_ray_stats(const rtx_ctx *c, rtx_ray_stats *out) { return get_stats(c, &rtx_ctx::ray_stats, out); }
 extern "C" int rtx_get_shadow_ray_stats(const rtx_ctx *c, rtx_shadow_ray_stats *out)
 {

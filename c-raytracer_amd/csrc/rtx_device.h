@@ -276,6 +276,8 @@ typedef struct DScene {
 	uint32_t ordbuf_waves; /* grid waves the buffer was sized for (0: none) */
 	uint32_t spec;         /* RTX_OPT_SHADOW_SPEC: a wave-uniform point of shininess 0 skips the specular factor of its
 	                        * samples (rtx_shadow.hip shade_terms_s0) */
+	uint32_t clearlane;    /* RTX_OPT_SHADOW_CLEARLANE: the all-clear points of a chunk are split off the processing order
+	                        * and shaded one per lane (rtx_shadow.hip k_shadow_clear) */
 } DScene;
 #define RTX_ORD_CAP 1024u                /* most samples of one emitter a point orders */
 #define RTX_ORD_BUCKETS 16u              /* buckets of the key */
@@ -356,6 +358,8 @@ enum {
 	RTX_C_SDARKPK,      /* count mode: ... of which in packets of dark rays alone */
 	RTX_C_SORDPT,       /* count mode: runs of one emitter's samples of a point walked in key order (order_begin) */
 	RTX_C_SORDRAY,      /* count mode: ... the shadow rays in them (the dark ones are not) */
+	RTX_C_CLPTS,        /* RTX_OPT_SHADOW_CLEARLANE: the clear list's length (k_clear_scan; k_shadow_clear reads it) */
+	RTX_C_CLRAYS,       /* ... the shadow rays of its points (k_shadow_clear counts them here, not in RTX_C_SHADOW) */
 	RTX_C_N
 };
 

@@ -470,6 +470,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	rtx_dark_stats ds = c0->dstats;
 	rtx_order_stats os = c0->ostats;
 	rtx_premask_stats ms = c0->mstats;
+	rtx_clearlane_stats cs = c0->cstats;
 	for (int r = 1; r < n; r++) {
 		const rtx_stats &o = g->ctx[r]->stats;
 		s.closest_rays += o.closest_rays;
@@ -501,6 +502,8 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 		os.shadow_ordered_points += g->ctx[r]->ostats.shadow_ordered_points;
 		os.shadow_ordered_rays += g->ctx[r]->ostats.shadow_ordered_rays;
 		ms.premask_points += g->ctx[r]->mstats.premask_points;
+		cs.clear_points += g->ctx[r]->cstats.clear_points;
+		cs.clear_rays += g->ctx[r]->cstats.clear_rays;
 		s.waves += o.waves;
 		s.chunks += o.chunks;
 		s.kernel_ms = std::max(s.kernel_ms, o.kernel_ms);
@@ -518,6 +521,7 @@ extern "C" int rtx_group_render(rtx_group *g, const rtx_frame *fr, const rtx_par
 	g->dstats = ds;
 	g->ostats = os;
 	g->mstats = ms;
+	g->cstats = cs;
 	return RTX_OK;
 }
 
@@ -598,6 +602,24 @@ extern "C" int rtx_group_device_premask_stats(const rtx_group *g, int r, rtx_pre
 	if (r < 0 || r >= g->n)
 		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
 	*out = g->ctx[r]->mstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_get_clearlane_stats(const rtx_group *g, rtx_clearlane_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	*out = g->cstats;
+	return RTX_OK;
+}
+
+extern "C" int rtx_group_device_clearlane_stats(const rtx_group *g, int r, rtx_clearlane_stats *out)
+{
+	if (!g || !out)
+		return fail(RTX_ERR_ARG, "null argument");
+	if (r < 0 || r >= g->n)
+		return fail(RTX_ERR_ARG, "device %d of a group of %d", r, g->n);
+	*out = g->ctx[r]->cstats;
 	return RTX_OK;
 }
 

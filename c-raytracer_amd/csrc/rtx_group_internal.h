@@ -42,6 +42,7 @@ struct rtx_group {
 	rtx_dark_stats dstats{};
 	rtx_order_stats ostats{};
 	rtx_premask_stats mstats{};
+	rtx_clearlane_stats cstats{};
 	/* rtx_group_render_passes / rtx_group_render_adaptive (rtx_group_passes.cpp), sized at the first call: the
 	 * travelling members' packed tile statistics and pass records on their own devices, and where device 0
 	 * receives them; the list as a group of one receives it from itself (rccl_self) */

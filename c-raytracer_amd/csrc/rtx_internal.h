@@ -183,6 +183,8 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float4> d_contrib;
 	DevBuf<uint32_t> d_ordbuf; /* k_shadow's order / result slices, RTX_ORD_WORDS words per grid wave (DScene.ordbuf) */
 	DevBuf<uint32_t> d_pmask; /* the chunk's per-point masks, a word per record (k_point_masks) */
+	DevBuf<uint32_t> d_clbuf; /* the chunk's processing order split into clear list and rest, and the split's prefix sums
+	                           * (RTX_OPT_SHADOW_CLEARLANE, rtx_clearlane_words) */
 	DevBuf<uint2> d_tile_rec;
 	/* shade points per tile seen by the last render of this scene with the same GI / bounce
 	 * settings: sizes the next render's chunks (the static estimate is 5x too high on scene6) */
@@ -202,6 +204,7 @@ struct rtx_ctx : CtxHandles {
 	rtx_dark_stats dstats{};  /* rtx_get_dark_stats */
 	rtx_order_stats ostats{}; /* rtx_get_order_stats */
 	rtx_premask_stats mstats{}; /* rtx_get_premask_stats */
+	rtx_clearlane_stats cstats{}; /* rtx_get_clearlane_stats */
 	/* ray queries (rtx_trace_rays*): counters of their own, the host-buffer call's device copies */
 	DevBuf<unsigned long long> d_rctr;
 	DevBuf<float4> d_qrays, d_qhits;
@@ -256,6 +259,7 @@ struct rtx_ctx : CtxHandles {
 	int opt_point = 1;        /* RTX_OPT_SHADOW_POINT: planes and listed objects decided once per shade point */
 	int opt_dark = 1;         /* RTX_OPT_SHADOW_DARK: light samples that add nothing skip their shadow query */
 	int opt_spec = 1;         /* RTX_OPT_SHADOW_SPEC: a shininess-0 point's samples skip the specular factor */
+	int opt_clearlane = 1;    /* RTX_OPT_SHADOW_CLEARLANE: the all-clear points shaded one per lane, in a kernel of their own */
 	int opt_order = 1;        /* RTX_OPT_SHADOW_ORDER: a walking point's light samples walked in key order */
 	int opt_premask = 1;      /* RTX_OPT_SHADOW_PREMASK: the per-point masks formed before k_shadow, one point per lane */
 	uint32_t opt_trace_pack = 1; /* RTX_OPT_TRACE_PACK: 0 off, 1 RTX_TRACE_PACK_SEG rays per segment, else that many */

@@ -79,7 +79,8 @@ hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *in, float *o
 hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes);
 hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm, uint32_t n_sp,
 			     uint32_t per_wave, uint32_t slot_b, float4 *contrib, unsigned long long *ctr, int count,
-			     uint32_t cus, hipStream_t stream, uint32_t *pmask, int *premasked);
+			     uint32_t cus, hipStream_t stream, uint32_t *pmask, int *premasked, uint32_t *clbuf, int *clearlane);
+size_t rtx_clearlane_words(uint32_t n_sp);
 hipError_t rtx_launch_shadow_rays(const DScene *S, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
 				  int slots, int count, uint32_t cus, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_shadow(void);

@@ -209,10 +209,19 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 			Ssh.ordbuf = c->d_ordbuf;
 			Ssh.ordbuf_waves = lanes / 64;
 		}
+		/* RTX_OPT_SHADOW_CLEARLANE: where the launch can take it (the masks formed ahead, wave-uniform packets, no
+		 * counting), 4 B per point more for the split processing order */
+		Ssh.clearlane = 0u;
+		if (c->opt_clearlane && c->opt_premask && Ssh.point && slot_b == 64 && !p->count_traversal && n_sp) {
+			HIP_TRY(c->d_clbuf.grow(rtx_clearlane_words((uint32_t)std::max<size_t>(n_sp, c->d_sp.bytes / (6 * sizeof(float4)))) *
+						sizeof(uint32_t)));
+			Ssh.clearlane = 1u;
+		}
 		int premasked = 0; /* RTX_OPT_SHADOW_PREMASK: k_point_masks ran for this chunk */
+		int clearlane = 0; /* ... and k_shadow_clear */
 		HIP_TRY(rtx_launch_shadow(&Ssh, &P, c->d_sp, perm, n_sp, per_wave, slot_b, c->d_contrib, c->d_ctr,
 					  p->count_traversal, (uint32_t)c->cus, stream, c->opt_premask ? c->d_pmask : nullptr,
-					  &premasked));
+					  &premasked, Ssh.clearlane ? (uint32_t *)c->d_clbuf : nullptr, &clearlane));
 		if (premasked)
 			premask_points += n_sp;
 		HIP_TRY(hipEventRecord(c->ev[2], stream));
@@ -249,7 +258,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	const unsigned long long *ctr = tot;
 	rtx_stats &st = c->stats;
 	st.closest_rays = ctr[RTX_C_CLOSEST];
-	st.shadow_rays = ctr[RTX_C_SHADOW];
+	st.shadow_rays = ctr[RTX_C_SHADOW] + ctr[RTX_C_CLRAYS]; /* k_shadow_clear counts its points' rays apart */
 	/* the threaded walk counts box tests; a node visit is a BVH2 inner node (two box tests) */
 	st.shadow_node_visits = ctr[RTX_C_SBOXES] / 2;
 	st.shadow_tri_tests = ctr[RTX_C_STRIS];
@@ -273,6 +282,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	c->ostats.shadow_ordered_points = ctr[RTX_C_SORDPT];
 	c->ostats.shadow_ordered_rays = ctr[RTX_C_SORDRAY];
 	c->mstats.premask_points = premask_points;
+	c->cstats.clear_points = ctr[RTX_C_CLPTS];
+	c->cstats.clear_rays = ctr[RTX_C_CLRAYS];
 	st.node_visits = ctr[RTX_C_NODES] + st.shadow_node_visits;
 	st.tri_tests = ctr[RTX_C_TRIS] + ctr[RTX_C_STRIS];
 	st.sphere_tests = ctr[RTX_C_SPHERES] + ctr[RTX_C_SSPHERES];
@@ -363,6 +374,7 @@ static int render_no_tiles(rtx_ctx *c)
 	c->dstats = rtx_dark_stats{};
 	c->ostats = rtx_order_stats{};
 	c->mstats = rtx_premask_stats{};
+	c->cstats = rtx_clearlane_stats{};
 	return RTX_OK;
 }
 

@@ -203,9 +203,9 @@ def write_stl(path, tris):
     _check_scene(scene_lib().rtx_stl_write(os.fsencode(path), tris.shape[0], tris.ctypes.data))
 
 
-def _with_point_stats(s, p, d=None, m=None, o=None):
-    """the rtx_point_stats (and rtx_dark_stats, rtx_premask_stats, rtx_order_stats) counters as attributes of the Stats
-    beside them"""
+def _with_point_stats(s, p, d=None, m=None, o=None, cl=None):
+    """the rtx_point_stats (and rtx_dark_stats, rtx_premask_stats, rtx_order_stats, rtx_clearlane_stats) counters as
+    attributes of the Stats beside them"""
     for f, _ in abi.PointStats._fields_:
         setattr(s, f, getattr(p, f))
     if d is not None:
@@ -217,6 +217,9 @@ def _with_point_stats(s, p, d=None, m=None, o=None):
     if o is not None:
         for f, _ in abi.OrderStats._fields_:
             setattr(s, f, getattr(o, f))
+    if cl is not None:
+        for f, _ in abi.ClearlaneStats._fields_:
+            setattr(s, f, getattr(cl, f))
     return s
 
 
@@ -306,7 +309,9 @@ class Renderer:
         _check(self.lib.rtx_get_premask_stats(self._ctx, C.byref(m)))
         o = abi.OrderStats()
         _check(self.lib.rtx_get_order_stats(self._ctx, C.byref(o)))
-        return _with_point_stats(s, p, d, m, o)
+        cl = abi.ClearlaneStats()
+        _check(self.lib.rtx_get_clearlane_stats(self._ctx, C.byref(cl)))
+        return _with_point_stats(s, p, d, m, o, cl)
 
     def trace_rays(self, origins, dirs, tmax=None, any_hit=False, reorder=False, count=False):
         """rtx_trace_rays on host arrays: origins / dirs (n, 3), tmax None (unbounded), a scalar or (n,).
@@ -788,7 +793,9 @@ class Group:
         _check(self.lib.rtx_group_get_premask_stats(self._g, C.byref(m)))
         o = abi.OrderStats()
         _check(self.lib.rtx_group_get_order_stats(self._g, C.byref(o)))
-        return _with_point_stats(s, p, d, m, o)
+        cl = abi.ClearlaneStats()
+        _check(self.lib.rtx_group_get_clearlane_stats(self._g, C.byref(cl)))
+        return _with_point_stats(s, p, d, m, o, cl)
 
     def device_stats(self, r):
         s = Stats()
@@ -801,7 +808,9 @@ class Group:
         _check(self.lib.rtx_group_device_premask_stats(self._g, r, C.byref(m)))
         o = abi.OrderStats()
         _check(self.lib.rtx_group_device_order_stats(self._g, r, C.byref(o)))
-        return _with_point_stats(s, p, d, m, o)
+        cl = abi.ClearlaneStats()
+        _check(self.lib.rtx_group_device_clearlane_stats(self._g, r, C.byref(cl)))
+        return _with_point_stats(s, p, d, m, o, cl)
 
     def render_passes(self, frame, params, passes, jitter=False, aperture=0.0, focus=1.0, target_error=0.0, min_passes=2):
         """rtx_group_render_passes on host arrays, as Renderer.render_passes: (rgb, z, variance); pass_stats() tells how

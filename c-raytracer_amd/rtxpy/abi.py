@@ -99,6 +99,11 @@ class PremaskStats(C.Structure):
     _fields_ = [("premask_points", C.c_uint64)]
 
 
+class ClearlaneStats(C.Structure):
+    """rtx_clearlane_stats: what RTX_OPT_SHADOW_CLEARLANE took (rtxpy's stats() set them on the Stats they return)"""
+    _fields_ = [("clear_points", C.c_uint64), ("clear_rays", C.c_uint64)]
+
+
 RTX_TRANSPORT_NONE, RTX_TRANSPORT_RCCL, RTX_TRANSPORT_LOOPBACK, RTX_TRANSPORT_RCCL_SELF = 0, 1, 2, 3
 
 
@@ -117,7 +122,7 @@ RTX_OPT_SHADOW_WALK, RTX_OPT_BVH_LEAF, RTX_OPT_SPSORT, RTX_OPT_SHADOW_SLOT, RTX_
     RTX_OPT_SHADOW_LDS_STACK, RTX_OPT_TRACE_WALK, RTX_OPT_TREE_FRAME, RTX_OPT_CHUNK_TILES, \
     RTX_OPT_SP_PER_TILE, RTX_OPT_SHADOW_CULL, RTX_OPT_RAYS_GRAB, RTX_OPT_RAYS_QUEUES, \
     RTX_OPT_SHADOW_POINT, RTX_OPT_SHADOW_DARK, RTX_OPT_SHADOW_PREMASK, RTX_OPT_SHADOW_ORDER, \
-    RTX_OPT_SHADOW_SPEC, RTX_OPT_TRACE_PACK = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19
+    RTX_OPT_SHADOW_SPEC, RTX_OPT_TRACE_PACK, RTX_OPT_SHADOW_CLEARLANE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20
 RTX_DOF_NONE, RTX_DOF_SCALE_BIAS, RTX_DOF_CAMERA = 0, 1, 2
 RTX_FALLOFF_QUAD, RTX_FALLOFF_LIN, RTX_FALLOFF_INV_QUAD = 0, 1, 2
 
@@ -288,13 +293,13 @@ KAT_NAMES = ["moller", "sphere", "plane", "slab", "noise", "texture", "sph_light
 
 # symbols include/rtx.h declares (checked by tests/test_abi.py)
 RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload_scene", "rtx_render",
-               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_order_stats", "rtx_get_premask_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
+               "rtx_render_device", "rtx_get_stats", "rtx_get_point_stats", "rtx_get_dark_stats", "rtx_get_order_stats", "rtx_get_premask_stats", "rtx_get_clearlane_stats", "rtx_close", "rtx_last_error", "rtx_kat", "rtx_postprocess",
                "rtx_postprocess_device", "rtx_set_builder", "rtx_set_option", "rtx_group_open", "rtx_group_open_loopback", "rtx_group_open_rccl_self", "rtx_group_size", "rtx_read_wide_tree", "rtx_read_bvh2",
                "rtx_group_set_builder", "rtx_group_set_option", "rtx_group_upload_scene", "rtx_group_render", "rtx_group_get_stats", "rtx_group_device_stats",
                "rtx_group_get_point_stats", "rtx_group_device_point_stats",
                "rtx_group_get_dark_stats", "rtx_group_device_dark_stats",
                "rtx_group_get_order_stats", "rtx_group_device_order_stats",
-               "rtx_group_get_premask_stats", "rtx_group_device_premask_stats",
+               "rtx_group_get_premask_stats", "rtx_group_device_premask_stats", "rtx_group_get_clearlane_stats", "rtx_group_device_clearlane_stats",
                "rtx_group_member_info", "rtx_group_close", "rtx_tile_pack_count", "rtx_tile_pack_host", "rtx_tile_unpack_host",
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
                "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
@@ -377,6 +382,8 @@ def declare_rtx(lib):
     lib.rtx_get_order_stats.restype = C.c_int
     lib.rtx_get_premask_stats.argtypes = [C.c_void_p, C.POINTER(PremaskStats)]
     lib.rtx_get_premask_stats.restype = C.c_int
+    lib.rtx_get_clearlane_stats.argtypes = [C.c_void_p, C.POINTER(ClearlaneStats)]
+    lib.rtx_get_clearlane_stats.restype = C.c_int
     lib.rtx_close.argtypes = [C.c_void_p]
     lib.rtx_close.restype = None
     lib.rtx_last_error.argtypes = []
@@ -433,6 +440,10 @@ def declare_rtx(lib):
     lib.rtx_group_get_premask_stats.restype = C.c_int
     lib.rtx_group_device_premask_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(PremaskStats)]
     lib.rtx_group_device_premask_stats.restype = C.c_int
+    lib.rtx_group_get_clearlane_stats.argtypes = [C.c_void_p, C.POINTER(ClearlaneStats)]
+    lib.rtx_group_get_clearlane_stats.restype = C.c_int
+    lib.rtx_group_device_clearlane_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(ClearlaneStats)]
+    lib.rtx_group_device_clearlane_stats.restype = C.c_int
     lib.rtx_group_member_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(GroupMember)]
     lib.rtx_group_member_info.restype = C.c_int
     lib.rtx_group_close.argtypes = [C.c_void_p]

@@ -277,6 +277,13 @@ typedef struct rtx_premask_stats {
 	                          * frame, or 0: the option is off or the scene is not one it applies to) */
 } rtx_premask_stats;
 
+/* What RTX_OPT_SHADOW_CLEARLANE took in the last render, with or without count_traversal (a counting render
+ * takes none); a struct of its own for the same reason (rtx_get_clearlane_stats, after the render) */
+typedef struct rtx_clearlane_stats {
+	uint64_t clear_points; /* shade points shaded one per lane by the kernel of the all-clear points */
+	uint64_t clear_rays;   /* their shadow rays (counted in rtx_stats.shadow_rays too) */
+} rtx_clearlane_stats;
+
 typedef struct rtx_ctx rtx_ctx;
 
 /* BVH builders for rtx_upload_scene (replacing accel_init, accel.c:266-315) */
@@ -306,6 +313,7 @@ int rtx_get_point_stats(const rtx_ctx *ctx, rtx_point_stats *out);
 int rtx_get_dark_stats(const rtx_ctx *ctx, rtx_dark_stats *out);
 int rtx_get_order_stats(const rtx_ctx *ctx, rtx_order_stats *out);
 int rtx_get_premask_stats(const rtx_ctx *ctx, rtx_premask_stats *out);
+int rtx_get_clearlane_stats(const rtx_ctx *ctx, rtx_clearlane_stats *out);
 /* Builder used by subsequent rtx_upload_scene calls on this context (RTX_BUILD_*). */
 int rtx_set_builder(rtx_ctx *ctx, int builder);
 
@@ -384,6 +392,12 @@ enum rtx_option {
 	                               * image, shade points and counters, bit for bit); 512, 1024, 2048 or 4096: the
 	                               * same with that many rays per segment (1 takes the library's own figure);
 	                               * 0: every batch of 64 rays walks to the end on its own */
+	RTX_OPT_SHADOW_CLEARLANE = 20, /* 1 (default): the shade points with 64 light samples or more that RTX_OPT_SHADOW_POINT
+	                               * finds clear of everything, and that lie on no emitter, are split off the
+	                               * processing order and shaded by a kernel of their own, one point per lane, its
+	                               * samples in sequence, summed in the order of the 64-lane reduction (same image,
+	                               * bit for bit).  Only where RTX_OPT_SHADOW_PREMASK formed the masks, and not in
+	                               * a render with count_traversal; 0: k_shadow shades them, one point per wave */
 };
 int rtx_set_option(rtx_ctx *ctx, int option, int64_t value);
 /* The frame rtx_upload_scene builds the scene's BVHs in under RTX_FRAME_AUTO (a diagnostic; no
@@ -556,6 +570,9 @@ int rtx_group_device_order_stats(const rtx_group *g, int r, rtx_order_stats *out
 /* rtx_premask_stats likewise */
 int rtx_group_get_premask_stats(const rtx_group *g, rtx_premask_stats *out);
 int rtx_group_device_premask_stats(const rtx_group *g, int r, rtx_premask_stats *out);
+/* rtx_clearlane_stats likewise */
+int rtx_group_get_clearlane_stats(const rtx_group *g, rtx_clearlane_stats *out);
+int rtx_group_device_clearlane_stats(const rtx_group *g, int r, rtx_clearlane_stats *out);
 /* What the runtime reports about member r, read back rather than assumed (a line that claims N
  * devices can show that N communicators of one clique formed on N distinct devices) */
 typedef struct rtx_group_member {
