@@ -27,9 +27,18 @@
  * samples fill whole power-of-two lane slots and its sum runs inside one wave
  * in lane order, so its result does not depend on which wave takes it.
  *
- * k_shadow_rays: the same shadow query (shadow_query) on a caller's shadow rays
- * (rtx_trace_shadow_rays), one 64-ray packet per wave, so tests can hold the walk
- * to brute force ray by ray.
+ * This file holds everything compiled into a k_shadow<...> instance: the intersection
+ * tests, both walks, shadow_query, sampling and shading, the per-point masks, the sample
+ * order and the kernel.  The rest of the translation unit (one object, because the device
+ * functions here are shared) is included at the end, a part each:
+ *   rtx_shadow_premask.h    k_point_masks: the per-point masks ahead of k_shadow
+ *   rtx_shadow_clearlane.h  the partition kernels and k_shadow_clear: all-clear points, one per lane
+ *   rtx_shadow_rays.h       k_shadow_rays: shadow_query on a caller's shadow rays
+ *                           (rtx_trace_shadow_rays)
+ *   rtx_shadow_kat.h        the known-answer-test kernels of the device functions here
+ *   rtx_shadow_launch.h     k_w8_fill and the host launch code
+ * Code that k_shadow executes stays in this file: bench.py ties a committed counter summary
+ * to the kernel by a hash of this file and of the headers included below, not of those parts.
  */
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -41,52 +50,46 @@
 #include "rtx_w8.h"
 #include "rtx_launch.h"
 
+/* The compile-time switches of this translation unit (rtx_w8.h has the 8-wide node test's, which k_trace
+ * shares).  Measurement only, the images are wrong: */
 #ifndef RTX_DEBUG_NOWALK
-#define RTX_DEBUG_NOWALK 0 /* measurement only: skip the BVH walk (everything else in k_shadow stays); 2: the walking
-                            * points' runs are still ordered (order_begin, the order reads, the result slots), 1: they
-                            * become all-clear points */
+#define RTX_DEBUG_NOWALK 0 /* skip the BVH walk; 1: walking points become all-clear points, 2: their runs are still ordered */
 #endif
 #ifndef RTX_DEBUG_NOLEAF
-#define RTX_DEBUG_NOLEAF 0 /* measurement only: the walk tests no leaf (wrong images; the cost of the leaf tests) */
+#define RTX_DEBUG_NOLEAF 0 /* the walk tests no leaf (the cost of the leaf tests) */
 #endif
-#ifndef RTX_SH_FASTSQRT
-#define RTX_SH_FASTSQRT 1 /* the shadow ray's length from v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence */
-#endif
-#ifndef RTX_SH_OCT
-#define RTX_SH_OCT 1 /* walks specialised on a wave-uniform direction octant */
-#endif
-#ifndef RTX_SH_FASTPOW
-#define RTX_SH_FASTPOW 1 /* specular powf from v_log_f32 / v_exp_f32 (sh_pow) */
-#endif
-#ifndef RTX_SH_FARLIN
-#define RTX_SH_FARLIN 0 /* far shade points: objects tested one by one are culled by their world boxes first */
-#endif
-#ifndef RTX_SH_SPILL_UNI
-#define RTX_SH_SPILL_UNI 1 /* the lane-stack spill area addressed from a wave-uniform base */
-#endif
-#ifndef RTX_SH_RECAFTER
-#define RTX_SH_RECAFTER 1 /* several points per packet: the record address formed again after the walk */
-#endif
-#ifndef RTX_SH_SPUNI
-#define RTX_SH_SPUNI 1 /* >= 64 lights: the shade-point record through scalar loads */
-#endif
+/* The occupancy the instances are register-capped for (__launch_bounds__): */
 #ifndef RTX_SHADOW_OCC_DEFAULT
 #define RTX_SHADOW_OCC_DEFAULT 8 /* waves per SIMD the walk is register-capped for */
 #endif
 #ifndef RTX_SHADOW_OCC_SLOT
 #define RTX_SHADOW_OCC_SLOT RTX_SHADOW_OCC_DEFAULT /* the same for the lane-slot kernel */
 #endif
-/* light_point (object.c:293-304) in k_shadow: a sphere light's inclination and azimuth are
- * u * 2pi, so their sines and cosines come from the revolution-scaled v_sin_f32 / v_cos_f32
- * instead of OCML's range-reduced sinf / cosf.  KAT: RTX_KAT_SPH_LIGHT_SH, <= 4e-6 of the
- * radius.  RTX_SH_FASTTRIG=0 restores the exact light_point. */
-#ifndef RTX_SH_FASTTRIG
-#define RTX_SH_FASTTRIG 1
+/* Tunable counts of the 8-wide walk (shadow_walk8): */
+#ifndef RTX_W8_TQ
+#define RTX_W8_TQ 4 /* deferred leaf groups per lane in LDS (besides the one in a register) */
 #endif
-/* 1/x in light sampling and attenuation: v_rcp_f32 (1 ulp) instead of the IEEE division
- * sequence (the closest-hit path keeps IEEE division).  RTX_SH_FASTDIV=0 restores it. */
+#ifndef RTX_W8_DEFER
+#define RTX_W8_DEFER 64 /* lanes holding deferred leaf tests that trigger a round of them (16 / 32 / 48 / 64: 613 / 601 / 598 / 594 ms) */
+#endif
+/* Numerical forms; 0 restores the reference's arithmetic (how a parity difference is bisected; the KATs name them): */
+#ifndef RTX_SH_FASTSQRT
+#define RTX_SH_FASTSQRT 1 /* the shadow ray's length from v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence */
+#endif
+#ifndef RTX_SH_FASTPOW
+#define RTX_SH_FASTPOW 1 /* specular powf from v_log_f32 / v_exp_f32 (sh_pow) */
+#endif
+#ifndef RTX_SH_FASTTRIG
+#define RTX_SH_FASTTRIG 1 /* a sphere light's sines and cosines from the revolution-scaled v_sin_f32 / v_cos_f32 (light_point_sh) */
+#endif
 #ifndef RTX_SH_FASTDIV
-#define RTX_SH_FASTDIV 1
+#define RTX_SH_FASTDIV 1 /* 1/x in light sampling and attenuation from v_rcp_f32 (1 ulp); the closest-hit path keeps IEEE division */
+#endif
+#ifndef RTX_SH_PLANE_RCP
+#define RTX_SH_PLANE_RCP 1 /* the plane test's quotient as num * v_rcp_f32(a) (plane_blocks) */
+#endif
+#ifndef RTX_SH_FARLIN
+#define RTX_SH_FARLIN 0 /* far shade points: objects tested one by one are culled by their world boxes first (1), spheres only (2) */
 #endif
 
 /* ------------------------------------------------------------------------ */
@@ -241,7 +244,7 @@ struct QBvh {
 	uint32_t wv;          /* this wave's index in its workgroup */
 	uint32_t lstk;        /* lane-stack entries in LDS (<= RTX_W8_STACK) */
 	lds_u32 *stk;         /* the wave's LDS stacks of sibling groups: lane l's entry k at stk[k * WAVE + l]
-	                       * (RTX_W8_LANEADDR 0: this lane's, entry k at stk[k * WAVE]) */
+	                       * (LA false: this lane's, entry k at stk[k * WAVE]) */
 	lds_u32 *tq;          /* WALK_W8: the LDS queues of deferred leaf groups, likewise */
 	bool sph;             /* WALK_W8: the tree holds spheres (DScene.w8sph) */
 };
@@ -333,35 +336,11 @@ __device__ __forceinline__ void shadow_walk(const QBvh &Q, const char *__restric
  *    register, the older groups in the lane's LDS stack (entries from Q.lstk on in HBM,
  *    Q.spill), at most one per level, so any depth walks.
  * tl < 0 on entry: inactive lane.  On an opaque hit tl becomes -1. */
-#ifndef RTX_SH_OWNINC
-#define RTX_SH_OWNINC 1 /* a slot's point found from the lane's previous one (off[] is nondecreasing) */
-#endif
-#ifndef RTX_SH_SLOTFOLD
-#define RTX_SH_SLOTFOLD 1 /* slot sums folded by lane 0 from LDS (k_shadow's several-points-per-packet path) */
-#endif
-#ifndef RTX_W8_TOP
-#define RTX_W8_TOP 1 /* divergent steps read the tree's top levels (DScene.w8top entries) from an LDS copy */
-#endif
-#ifndef RTX_W8_TQ
-#define RTX_W8_TQ 4 /* deferred leaf groups per lane in LDS (besides the one in a register) */
-#endif
-#ifndef RTX_W8_TRIONLY
-#define RTX_W8_TRIONLY 1 /* leaf tests of a tree without spheres skip the sphere case (DScene.w8sph) */
-#endif
-#ifndef RTX_W8_LANEADDR
-#define RTX_W8_LANEADDR 2 /* the lane-stack / queue LDS addresses formed from lane_id() at each access (no per-lane
-                           * address register live across the walk, which the allocator spilled to scratch) */
-#endif
+/* LA (the lane-slot kernels): the lane-stack / queue LDS addresses are formed from lane_id() at each access,
+ * so no per-lane address register lives across the walk (the allocator spilled it to scratch there);
+ * else Q.stk / Q.tq are this lane's own */
 #define W8_LN (LA ? lane_id() : 0u)
-#ifndef RTX_W8_LEAF2
-#define RTX_W8_LEAF2 1 /* a round of opaque leaf tests takes two of a lane's hit leaf slots */
-#endif
-#ifndef RTX_W8_DEFER2
-#define RTX_W8_DEFER2 1 /* a round of deferred transparent-leaf tests takes two of a lane's queued leaves */
-#endif
-#ifndef RTX_W8_DEFER
-#define RTX_W8_DEFER 64 /* lanes holding deferred leaf tests that trigger a round of them (16 / 32 / 48 / 64: 613 / 601 / 598 / 594 ms) */
-#endif
+
 /* a deferred leaf test: the transparent primitive at entry pr (rtx_device.h DW8 leaf entry,
  * whose 4th float4 holds its material's kt) against this lane's shadow ray; a hit multiplies
  * the transmittance (accel.c:370-377) */
@@ -433,27 +412,21 @@ struct W8Ctr {
 };
 
 /* this lane's opaque leaf hits lm (visit order) in the block at base, tested in turn: does one
- * block the ray?  (the wave's lanes in step, a lane leaving at its first blocking hit) */
+ * block the ray?  (the wave's lanes in step, a lane leaving at its first blocking hit).  A round takes
+ * two of the lane's hit leaves (the same tests in the same order, half the rounds: a Menger face's two
+ * triangles share a box in the rotated frame, so a lane that meets one meets both) */
 template <bool COUNT, bool SPH, uint32_t K>
 __device__ __forceinline__ bool w8_opaque_leaves(const DW8 *w8, uint32_t lm, uint32_t base, f3 o, f3 d, float tl, W8Ctr &c)
 {
 	while (lm) {
 		const uint32_t p = __builtin_ctz(lm);
 		lm &= lm - 1;
-		if (RTX_W8_LEAF2) {
-			/* two of the lane's hit leaves per round (the same tests in the same order, half the
-			 * rounds: a Menger face's two triangles share a box in the rotated frame, so a lane that
-			 * meets one meets both) */
-			const bool two = lm != 0;
-			const uint32_t q = two ? __builtin_ctz(lm) : p;
-			lm &= lm - 1;
-			if (w8_opaque_test<COUNT, SPH>((const char *)(w8 + base + (p ^ K)), o, d, tl, c.ntri, c.nsph))
-				return true;
-			if (two && w8_opaque_test<COUNT, SPH>((const char *)(w8 + base + (q ^ K)), o, d, tl, c.ntri, c.nsph))
-				return true;
-			continue;
-		}
+		const bool two = lm != 0;
+		const uint32_t q = two ? __builtin_ctz(lm) : p;
+		lm &= lm - 1;
 		if (w8_opaque_test<COUNT, SPH>((const char *)(w8 + base + (p ^ K)), o, d, tl, c.ntri, c.nsph))
+			return true;
+		if (two && w8_opaque_test<COUNT, SPH>((const char *)(w8 + base + (q ^ K)), o, d, tl, c.ntri, c.nsph))
 			return true;
 	}
 	return false;
@@ -478,10 +451,10 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 			w.tgrp &= w.tgrp - 1;
 			if (!(w.tgrp & 0xFFu))
 				w.tgrp = w.tn ? tq[--w.tn * WAVE + W8_LN] : 0u;
-			/* RTX_W8_DEFER2: the lane's next queued leaf in the same round (the transmittance
-			 * products in the same order) */
+			/* the lane's next queued leaf in the same round (the transmittance products in the same
+			 * order) */
 			const char *pr2 = nullptr;
-			if (RTX_W8_DEFER2 && w.tgrp) {
+			if (w.tgrp) {
 				pr2 = (const char *)(Q.w8 + (w.tgrp >> 8) + (__builtin_ctz(w.tgrp) ^ K));
 				w.tgrp &= w.tgrp - 1;
 				if (!(w.tgrp & 0xFFu))
@@ -489,13 +462,13 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 			}
 			/* not counted here: a deferred test counts where its leaf is queued (below) */
 			uint32_t n0 = 0, n1 = 0;
-			if (!RTX_W8_TRIONLY || Q.sph) {
+			if (Q.sph) {
 				w8_defer_test<false, true>(pr, o, d, tl, li, n0, n1);
-				if (RTX_W8_DEFER2 && pr2)
+				if (pr2)
 					w8_defer_test<false, true>(pr2, o, d, tl, li, n0, n1);
-			} else {
+			} else { /* a tree without spheres: the triangle test alone */
 				w8_defer_test<false, false>(pr, o, d, tl, li, n0, n1);
-				if (RTX_W8_DEFER2 && pr2)
+				if (pr2)
 					w8_defer_test<false, false>(pr2, o, d, tl, li, n0, n1);
 			}
 		}
@@ -551,7 +524,7 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 			 * it was tested by then depends on the rays that share its packet */
 			for (uint32_t m = dm; m; m &= m - 1) {
 				const char *pr = (const char *)(Q.w8 + base + (__builtin_ctz(m) ^ K));
-				if ((!RTX_W8_TRIONLY || Q.sph) && (__float_as_uint(ldg4(pr, 32).w) >> 24) == RTX_SPHERE)
+				if (Q.sph && (__float_as_uint(ldg4(pr, 32).w) >> 24) == RTX_SPHERE)
 					c.nsph++;
 				else
 					c.ntri++;
@@ -607,14 +580,13 @@ __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 o
 		for (uint32_t m = lm;; m &= m - 1) {
 			if (!ballot(m != 0))
 				break;
-			if (RTX_W8_LEAF2)
-				m &= m - 1;
+			m &= m - 1; /* two leaves a round (w8_opaque_leaves) */
 			r++;
 		}
 		c.nlr += r;
 	}
-	const bool blocked = (!RTX_W8_TRIONLY || Q.sph) ? w8_opaque_leaves<COUNT, true, K>(Q.w8, lm, base, o, d, tl, c)
-							  : w8_opaque_leaves<COUNT, false, K>(Q.w8, lm, base, o, d, tl, c);
+	const bool blocked = Q.sph ? w8_opaque_leaves<COUNT, true, K>(Q.w8, lm, base, o, d, tl, c)
+				   : w8_opaque_leaves<COUNT, false, K>(Q.w8, lm, base, o, d, tl, c);
 	if (blocked) { /* the queue too: a full queue left behind would keep the wave in deferred rounds */
 		tl = -1.f;
 		w.node = RTX_NONE;
@@ -680,9 +652,6 @@ __device__ __forceinline__ void shadow_walk8(const QBvh &Q, const DMaterial *__r
  * quotient t = num / a as num * v_rcp_f32(a) (within 2 ulp of the IEEE quotient, like the
  * light points of RTX_SH_FASTTRIG): the decisions differ from the IEEE test only for a t within
  * 2 ulp of the plane's epsilon or of the light sample's distance */
-#ifndef RTX_SH_PLANE_RCP
-#define RTX_SH_PLANE_RCP 1
-#endif
 __device__ __forceinline__ bool plane_blocks(f3 n, float dd, f3 o, f3 d, float eps, float dist)
 {
 	float t;
@@ -778,7 +747,7 @@ __device__ __forceinline__ bool shadow_query(const QBvh &Q, const char *__restri
 	const uint32_t oct = ((~__float_as_uint(inv.x)) >> 31) | (((~__float_as_uint(inv.y)) >> 31) << 1) |
 			     (((~__float_as_uint(inv.z)) >> 31) << 2);
 	const uint32_t lead = readlane(oct, (uint32_t)__ffsll((long long)live) - 1);
-	const uint32_t sel = (!RTX_SH_OCT || ballot(alive & (oct != lead))) ? 8u : lead;
+	const uint32_t sel = ballot(alive & (oct != lead)) ? 8u : lead;
 	switch (sel) {
 #define RTX_WALK(K)                                                                            \
 	case K:                                                                                \
@@ -1111,7 +1080,7 @@ __device__ __forceinline__ QBvh make_qbvh(const KShadow &ks, const uint4 *top_q,
 	Q.w8 = WALK == WALK_W8 ? unip(ks.w8) : nullptr;
 	Q.w8s = WALK == WALK_W8 ? unip(ks.w8s) : nullptr;
 	Q.t8 = t8;
-	Q.nt8 = (WALK == WALK_W8 && RTX_W8_TOP) ? min(uni(ks.w8top), (uint32_t)RTX_W8_TOP_MAX) : 0u;
+	Q.nt8 = WALK == WALK_W8 ? min(uni(ks.w8top), (uint32_t)RTX_W8_TOP_MAX) : 0u;
 	Q.spill = WALK == WALK_W8 ? unip(ks.w8spill) : nullptr;
 	Q.wv = wv;
 	Q.lstk = uni(ks.w8lstk);
@@ -1271,98 +1240,10 @@ __device__ __forceinline__ PointMasks point_masks(const KShadow &ks, f3 p, uint3
 	return m;
 }
 
-/* point_masks ahead of k_shadow (RTX_OPT_SHADOW_PREMASK), one shade point per lane: in point_masks a
- * whole wave works on one point, and all but its two sphere passes is wave-uniform arithmetic done 64
- * times over for one answer.  Here lane i takes record i of the chunk and walks the emitters, the
- * planes, the cull spheres and the listed records' spheres in turn, each read through the scalar
- * cache at a wave-uniform index, through the very functions point_masks calls (this file's compile
- * flags, -ffp-contract=off, hold for both), so every predicate has the same operands and the same
- * answer.  Scenes of at most 8 emitters only: the word written for record i is
- * cone | pln << 8 | lin << 16 | smp << 24, bit e of each byte for emitter e, and 0 for a far point
- * (point_masks gives a far point no mask).  k_shadow reads it where it would call point_masks.
- * Every shade point has a light sample (k_trace emits no other), so a point that is not far samples
- * some emitter and its smp byte is not 0: the byte tells the far points apart. */
-#define RTX_PM_BLOCK 256
-__global__ __launch_bounds__(RTX_PM_BLOCK) void k_point_masks(KShadow ks, uint32_t *__restrict__ out)
-{
-	const uint32_t i = blockIdx.x * RTX_PM_BLOCK + threadIdx.x;
-	const bool own = i < ks.n_sp;
-	const float4 *rec = ks.sp + (size_t)(own ? i : ks.n_sp - 1u) * SPREC;
-	const float4 q0 = ldg4(rec, 0), q4 = ldg4(rec, 64);
-	const f3 p = mk3(q0.x, q0.y, q0.z);
-	const uint32_t ow = __float_as_uint(q4.x), obj = ow & ~RTX_SP_FAR;
-	const bool live = own && !(ow & RTX_SP_FAR);
-	const bool pt = ks.point != 0;
-	const uint32_t n = min(ks.num_cull, (uint32_t)WAVE);
-	const uint32_t ne = min(ks.num_emitters, 8u);
-	const uint32_t num_lin = ks.num_lin, num_planes = ks.num_planes;
-	const uint32_t nr = pt ? min(ks.num_lsph, (uint32_t)WAVE) : 0u;
-	const bool lin_ok = pt && nr == num_lin;
-	uint32_t cone = 0u, pln = 0u, lin = 0u, smp = 0u;
-	for (uint32_t e = 0; e < ne; e++) {
-		const DEmitter E = emitter_uni(ks.emitters + e);
-		const uint32_t bit = 1u << e;
-		if (E.obj != obj)
-			smp |= bit;
-		f3 lc;
-		float lr;
-		emitter_sphere(E, lc, lr);
-		const f3 ax0 = sub3(lc, p);
-		const float L = sqrtf(magsqr3(ax0));
-		if (pt) {
-			bool pc = true;
-			for (uint32_t k = 0; k < num_planes; k++) {
-				const auto *pl = cptr(ks.planes) + k;
-				pc = plane_clear(mk3(pl->n[0], pl->n[1], pl->n[2]), pl->d, pl->eps, p, lc, lr, L) && pc;
-			}
-			if (pc)
-				pln |= bit;
-			if (!num_lin)
-				lin |= bit;
-		}
-		/* a lane whose point has no cone toward e (at or inside the light's sphere) counts as met */
-		const bool go = live && L > 1.01f * lr;
-		if ((!n && !nr) || !ballot(go))
-			continue;
-		const Cone c = cone_of(p, lc, lr, ax0, L);
-		if (n) {
-			/* four spheres a turn, their scalar loads issued together (one wait, not four; past the
-			 * last sphere the last one again), until every lane of the wave has met one */
-			bool meets = !go;
-			for (uint32_t k = 0; k < n && ballot(!meets); k += 4) {
-				f4v s[4];
-#pragma unroll
-				for (uint32_t j = 0; j < 4; j++)
-					s[j] = *(const __attribute__((address_space(4))) f4v *)(ks.cull + min(k + j, n - 1u));
-#pragma unroll
-				for (uint32_t j = 0; j < 4; j++)
-					meets = cone_meets<false>(c, p, make_float4(s[j].x, s[j].y, s[j].z, s[j].w)) || meets;
-			}
-			if (!meets)
-				cone |= bit;
-		}
-		if (lin_ok && nr) {
-			bool meets = !go;
-			for (uint32_t k = 0; k < nr && ballot(!meets); k++) {
-				const uint32_t ro = cptr((const uint32_t *)(ks.lin + k))[0]; /* DEmitter.obj */
-				const f4v s = *(const __attribute__((address_space(4))) f4v *)(ks.lsph + k);
-				meets = meets || (ro != E.obj && cone_meets<true>(c, p, make_float4(s.x, s.y, s.z, s.w)));
-			}
-			if (!meets)
-				lin |= bit;
-		}
-	}
-	if (own)
-		out[i] = live ? (cone | pln << 8 | lin << 16 | smp << 24) : 0u;
-}
-
-/* The lane-slot path's cone mask (RTX_SH_SLOTCULL): each lane tests its own point's cones (emitters
+/* The lane-slot path's cone mask (RTX_OPT_SHADOW_CULL 2): each lane tests its own point's cones (emitters
  * e < 8) against every sphere in turn, the sphere and the emitter read through the scalar cache;
  * bit e set when no sphere meets.  A packet whose every live lane is clear for its emitter skips
  * the walk, as a clear point's packets do on the wave-uniform path. */
-#ifndef RTX_SH_SLOTCULL
-#define RTX_SH_SLOTCULL 1
-#endif
 __device__ __forceinline__ uint32_t cone_mask_lane(const KShadow &ks, f3 p, bool own)
 {
 	const uint32_t n = uni(ks.num_cull);
@@ -1436,7 +1317,7 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	 * 64-bit address did, and the allocator spilled it to scratch around the generic-octant walk,
 	 * one store per packet (scene6: 43 GB of WRITE_SIZE per frame) */
 	const float4 *rec = UNI ? rec_uni : unip(ks.sp) + (size_t)sidv * SPREC;
-	const float4 q0 = sp_field<UNI && RTX_SH_SPUNI>(rec, 0), q4 = sp_field<UNI && RTX_SH_SPUNI>(rec, 4);
+	const float4 q0 = sp_field<UNI>(rec, 0), q4 = sp_field<UNI>(rec, 4);
 	const f3 p = mk3(q0.x, q0.y, q0.z);
 	const uint32_t obj = __float_as_uint(q4.x) & ~RTX_SP_FAR, far = __float_as_uint(q4.x) & RTX_SP_FAR;
 	const DEmitter *emitters = unip(ks.emitters);
@@ -1493,7 +1374,7 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 	bool qry = act;
 	bool none = false;
 	if (UNI && DK && uni(ks.dark) && !far && !clear) {
-		qry = act && !sample_dark<UNI && RTX_SH_SPUNI>(ks, rec, ldir, li, attf, act);
+		qry = act && !sample_dark<UNI>(ks, rec, ldir, li, attf, act);
 		none = !ballot(qry);
 	}
 	const QBvh Q = make_qbvh<WALK>(ks, top_q, top_e, stk, t8, wv);
@@ -1515,13 +1396,13 @@ __device__ __forceinline__ f3 light_sample(const KShadow &ks, const float4 *rec_
 							 (UNI && (rclr || none)) ? 0u : uni(ks.num_lin), have_tree, ks.tf, qry, far != 0, p, ldir,
 							 ldist, eobj, li, sc);
 	reread_barrier();
-	if (!UNI && RTX_SH_RECAFTER) {
+	if (!UNI) {
 		asm volatile("" : "+v"(sidv));
 		rec = unip(ks.sp) + (size_t)sidv * SPREC;
 	}
 	f3 contribution = mk3(0.f, 0.f, 0.f);
 	if (qry && !blocked)
-		contribution = shade_light<UNI && RTX_SH_SPUNI>(ks, rec, ldir, li, attf);
+		contribution = shade_light<UNI>(ks, rec, ldir, li, attf);
 	return contribution;
 }
 
@@ -1664,7 +1545,7 @@ __device__ __forceinline__ uint32_t order_key(const KShadow &ks, const float4 *r
 	const float attf = sample_att(ks, ldist, dsq);
 	dark = false;
 	if (dk_on)
-		dark = sample_dark<RTX_SH_SPUNI>(ks, rec, ldir, li, attf, act);
+		dark = sample_dark<true>(ks, rec, ldir, li, attf, act);
 	const float x = ldist * dot3(ldir, b) * ilr;
 	if (xo)
 		*xo = x;
@@ -1828,13 +1709,13 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 	__shared__ uint4 top_q[TOP ? RTX_TOP_MAX : 1];    /* the top records (rtx_device.h RTX_QTOP_CUT) */
 	__shared__ uint32_t top_e[TOP ? RTX_TOP_MAX : 1]; /* cut records: the DQNode index after the subtree */
 	/* the wide walks' lane stacks (16-byte aligned: the slot fold below reuses a wave's stack area as
-	 * float4 records, RTX_SH_SLOTFOLD) */
+	 * float4 records) */
 	__shared__ __attribute__((aligned(16))) uint32_t wstk[RTX_SH_NW][WALK == WALK_W8 ? RTX_W8_STACK + RTX_W8_TQ : 1][WAVE];
 	static_assert(WALK != WALK_W8 || (RTX_W8_STACK + RTX_W8_TQ) * WAVE * sizeof(uint32_t) >= WAVE * sizeof(float4),
 		      "a wave's lane-stack area must hold one float4 per lane for the slot fold");
 	__shared__ KShadow ks_s; /* the arguments, one copy for the workgroup */
 	/* WALK_W8: the 8-wide tree's top levels (RTX_W8_TOP_LEVELS), read by divergent steps from LDS */
-	__shared__ uint4 t8[WALK == WALK_W8 && RTX_W8_TOP ? RTX_W8_TOP_MAX * 4 : 1];
+	__shared__ uint4 t8[WALK == WALK_W8 ? RTX_W8_TOP_MAX * 4 : 1];
 	/* one wave's tables in one struct, so every lane addresses them from one base register */
 	struct WaveTables {
 		uint32_t off[WAVE + 1]; /* first lane slot of each shade point, total */
@@ -1852,7 +1733,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 		top_q[i] = ldg4u(ka.top + 4 * i);
 		top_e[i] = gptr(ka.top)[4 * ntop + i];
 	}
-	const uint32_t nt8 = (WALK == WALK_W8 && RTX_W8_TOP) ? min(ka.w8top, (uint32_t)RTX_W8_TOP_MAX) : 0u;
+	const uint32_t nt8 = WALK == WALK_W8 ? min(ka.w8top, (uint32_t)RTX_W8_TOP_MAX) : 0u;
 	for (uint32_t i = threadIdx.x; i < 4 * nt8; i += WAVE * RTX_SH_NW)
 		t8[i] = ldg4u((const uint32_t *)ka.w8 + 4 * i);
 	const uint32_t wv = uni(threadIdx.x / WAVE);
@@ -1863,14 +1744,13 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 	uint32_t *off = wt_w[wv].off, *nls = wt_w[wv].nls, *sid = wt_w[wv].sid;
 	uint8_t *clr = wt_w[wv].clr;
 	float(*Ls)[WAVE] = wt_w[wv].Ls;
-	/* the lane-stack addresses: per lane, or formed from lane_id() at each access (RTX_W8_LANEADDR; 2:
-	 * the lane-slot kernel only, whose allocation spilled the per-lane address and reloaded it at
-	 * every push and pop) */
-	constexpr bool LA = RTX_W8_LANEADDR == 2 ? (PATH == 2 || PATH == 3) : RTX_W8_LANEADDR != 0;
+	/* the lane-stack addresses: per lane, or formed from lane_id() at each access in the lane-slot
+	 * kernels, whose allocation spilled the per-lane address and reloaded it at every push and pop */
+	constexpr bool LA = PATH == 2 || PATH == 3;
 	/* the lane-slot path's cone cull (RTX_OPT_SHADOW_CULL 2) lives in its own instance, PATH 3, so
 	 * the default lane-slot kernel keeps its register allocation (with the code present but off,
 	 * scene6's k_shadow took 1083.4 against 1074.8 ms) */
-	constexpr bool SC = RTX_SH_SLOTCULL && WALK == WALK_W8 && (PATH == 3 || PATH == 0);
+	constexpr bool SC = WALK == WALK_W8 && (PATH == 3 || PATH == 0);
 	/* the dark samples (RTX_OPT_SHADOW_DARK) live in an instance of their own too, PATH 4: PATH 1 with
 	 * sample_dark, launched where the option is on and the scene walks a tree.  A scene without a
 	 * tree keeps PATH 1 as it was (with the code present but off, scene3's k_shadow took 52.7
@@ -2071,15 +1951,11 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 					break;
 				const uint32_t slot = base + (lane_id() >> slot_lg);
 				uint32_t k = 0;
-				if (slot < tot) {
-					if (RTX_SH_OWNINC) { /* owner_of from the previous packet's owner: a step or two, not six */
-						k = kp;
-						while (off[k + 1] <= slot)
-							k++;
-						kp = k;
-					} else {
-						k = owner_of(off, slot);
-					}
+				if (slot < tot) { /* the slot's point (rtx_wave.h owner_of) from the previous packet's: a step or two, not six */
+					k = kp;
+					while (off[k + 1] <= slot)
+						k++;
+					kp = k;
 				}
 				const uint32_t idx = ((slot - off[k]) << slot_lg) + (lane_id() & (slot_b - 1));
 				const bool act = slot < tot && idx < nls[k];
@@ -2118,7 +1994,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 					v.z += lane_xor_f<1>(v.z);
 				}
 				const uint32_t ns = min(t2 - base, spp);
-				if (WALK == WALK_W8 && RTX_SH_SLOTFOLD) {
+				if (WALK == WALK_W8) {
 					/* the same fold with the slot sums handed over in LDS instead of v_readlane (four
 					 * single-issue reads and three adds on SGPR operands per slot): each slot's first
 					 * lane stores (sum, point) in the wave's lane-stack area, empty between walks, and
@@ -2154,6 +2030,7 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 					base += spp;
 					continue;
 				}
+				/* the BVH2 instances (no lane-stack area to hand the sums over in): the fold by v_readlane */
 				uint32_t kc = readlane(k, 0);
 				float rx = Ls[0][kc], ry = Ls[1][kc], rz = Ls[2][kc];
 				for (uint32_t j = 0; j < ns; j++) {
@@ -2221,976 +2098,12 @@ __global__ __launch_bounds__(WAVE *RTX_SH_NW, OCC) void k_shadow(KShadow ka)
 }
 
 /* ------------------------------------------------------------------------ */
-/* k_shadow_clear: the all-clear points, one per lane (RTX_OPT_SHADOW_CLEARLANE) */
+/* the rest of this translation unit (one object: the device functions above are shared) */
 /* ------------------------------------------------------------------------ */
-/* An all-clear point (clear_run) needs neither the walk nor the layout made for it: in k_shadow a whole
- * wave reads one record, searches the emitter table, forms the draws' mix and reduces three butterflies
- * per point, and nearly every operand of its sample loop is a scalar.  Here the chunk's points are split
- * first (k_clear_count, k_clear_scan, k_clear_scatter: a stable partition of the processing order by
- * clear_lane_point), k_shadow takes the rest as before, and k_shadow_clear takes the clear list, a point
- * per lane, the samples in sequence.
- *   The clear list holds the points that pass k_shadow's all-clear predicate on their mask word and whose
- * smp byte names every emitter: the point lies on no emitter, so sample idx belongs to the same emitter
- * for every one of them and the sample index and the emitter stay wave-uniform. */
-#define RTX_CL_BLOCK 256
-#define RTX_CL_ITEMS 1024 /* positions of the processing order per workgroup of the partition */
-
-__device__ __forceinline__ bool clear_lane_point(uint32_t w, bool tree, uint32_t point, uint32_t all)
-{
-	const uint32_t smp = w >> 24, ok = (w >> 8) & (w >> 16) & (tree ? w : ~0u) & 0xffu;
-	const bool ac = point != 0 && smp && !(smp & ~ok); /* k_shadow's, word for word */
-	return ac && smp == all;
-}
-
-/* position i of the processing order: its record index, and whether it goes to the clear list */
-__device__ __forceinline__ bool clear_lane_at(const KShadow &ks, uint32_t i, uint32_t &sid)
-{
-	const bool tree = ks.have_tree != 0 && RTX_DEBUG_NOWALK != 1;
-	sid = 0u;
-	if (i >= ks.n_sp)
-		return false;
-	sid = ks.perm ? ks.perm[i] : i;
-	return clear_lane_point(ks.pm[sid], tree, ks.point, (1u << ks.num_emitters) - 1u);
-}
-
-/* the clear points among each workgroup's RTX_CL_ITEMS positions */
-__global__ __launch_bounds__(RTX_CL_BLOCK) void k_clear_count(KShadow ks, uint32_t *__restrict__ cnt)
-{
-	__shared__ uint32_t wc[RTX_CL_BLOCK / WAVE];
-	uint32_t c = 0;
-	for (uint32_t r = 0; r < RTX_CL_ITEMS / RTX_CL_BLOCK; r++) {
-		uint32_t sid;
-		c += popc64(ballot(clear_lane_at(ks, blockIdx.x * RTX_CL_ITEMS + r * RTX_CL_BLOCK + threadIdx.x, sid)));
-	}
-	if (lane_id() == 0)
-		wc[threadIdx.x / WAVE] = c;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t t = 0;
-		for (uint32_t w = 0; w < RTX_CL_BLOCK / WAVE; w++)
-			t += wc[w];
-		cnt[blockIdx.x] = t;
-	}
-}
-
-/* one workgroup: the counts' exclusive prefix sums in place, and their total, the clear list's length, to
- * RTX_C_CLPTS (k_shadow_clear reads it there) and to k_shadow's queue head: the rest list follows the
- * clear list in one array, and k_shadow, given the whole array, begins behind the clear list */
-__global__ __launch_bounds__(1024) void k_clear_scan(uint32_t *__restrict__ cnt, uint32_t nb, unsigned long long *__restrict__ ctr)
-{
-	__shared__ uint32_t part[1024];
-	const uint32_t per = (nb + 1023u) / 1024u, lo = min(threadIdx.x * per, nb), hi = min(lo + per, nb);
-	uint32_t s = 0;
-	for (uint32_t i = lo; i < hi; i++)
-		s += cnt[i];
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024u; d <<= 1) {
-		const uint32_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-		__syncthreads();
-		part[threadIdx.x] += v;
-		__syncthreads();
-	}
-	uint32_t run = part[threadIdx.x] - s;
-	for (uint32_t i = lo; i < hi; i++) {
-		const uint32_t c = cnt[i];
-		cnt[i] = run;
-		run += c;
-	}
-	if (threadIdx.x == 1023u) {
-		ctr[RTX_C_CLPTS] = part[1023];
-		ctr[RTX_C_SPQUEUE] = part[1023];
-	}
-}
-
-/* out = clear list | rest list, each in the processing order: a clear point goes to the number of clear
- * points before it, any other behind the clear list to the number of other points before it */
-__global__ __launch_bounds__(RTX_CL_BLOCK) void k_clear_scatter(KShadow ks, const uint32_t *__restrict__ off, uint32_t *__restrict__ out)
-{
-	__shared__ uint32_t wc[RTX_CL_BLOCK / WAVE];
-	const uint32_t nc = (uint32_t)ks.ctr[RTX_C_CLPTS], wv = threadIdx.x / WAVE;
-	uint32_t run = off[blockIdx.x];
-	for (uint32_t r = 0; r < RTX_CL_ITEMS / RTX_CL_BLOCK; r++) {
-		const uint32_t i = blockIdx.x * RTX_CL_ITEMS + r * RTX_CL_BLOCK + threadIdx.x;
-		uint32_t sid;
-		const bool f = clear_lane_at(ks, i, sid);
-		const u64 m = ballot(f);
-		__syncthreads(); /* the round before has read wc */
-		if (lane_id() == 0)
-			wc[wv] = popc64(m);
-		__syncthreads();
-		uint32_t before = run + mbcnt(m), all = 0;
-		for (uint32_t w = 0; w < RTX_CL_BLOCK / WAVE; w++) {
-			before += w < wv ? wc[w] : 0u;
-			all += wc[w];
-		}
-		if (i < ks.n_sp)
-			out[f ? before : nc + (i - before)] = sid;
-		run += all;
-	}
-}
-
-/* a float in a vector register of its own, so the arithmetic on it takes the two-VGPR forms */
-__device__ __forceinline__ float in_vgpr(float x)
-{
-	asm("" : "+v"(x));
-	return x;
-}
-
-/* what the sample loop reads of an emitter, per lane: k_shadow holds them in scalar registers, and a
- * scalar operand keeps an add, mul or fma from dual issue */
-struct EmLane {
-	uint32_t type, num_lights;
-	f3 li, p0, p1, p2;
-	float radius;
-};
-__device__ __forceinline__ void st3(float *d, f3 v)
-{
-	d[0] = v.x;
-	d[1] = v.y;
-	d[2] = v.z;
-}
-__device__ __forceinline__ EmLane emitter_lanes(const DEmitter &E)
-{
-	EmLane v;
-	v.type = E.type;
-	v.num_lights = E.num_lights;
-	v.li = mk3(in_vgpr(E.li[0]), in_vgpr(E.li[1]), in_vgpr(E.li[2]));
-	v.p0 = mk3(in_vgpr(E.p0[0]), in_vgpr(E.p0[1]), in_vgpr(E.p0[2]));
-	v.p1 = v.p2 = v.p0;
-	if (E.type != RTX_SPHERE) { /* a sphere light reads neither */
-		v.p1 = mk3(in_vgpr(E.p1[0]), in_vgpr(E.p1[1]), in_vgpr(E.p1[2]));
-		v.p2 = mk3(in_vgpr(E.p2[0]), in_vgpr(E.p2[1]), in_vgpr(E.p2[2]));
-	}
-	v.radius = in_vgpr(E.radius);
-	return v;
-}
-
-/* The light sum of this lane's point, today's bit for bit.  In k_shadow lane l adds samples l, l + 64, ...
- * to a sum that starts at +0, and wave_sum adds lane ^ M's value for M = 32, 16, ..., 1; lane 0's total
- * is a binary tree over the lanes' sums whose leaves, left to right, are lanes 0, 32, 16, 48, ...: the
- * 6-bit reversal of 0, 1, 2, ....  So leaf t is lane l = rev6(t): its samples in index order (each inside
- * its emitter's range: the packets clear_run hands to light_sample give the same terms), then the tree
- * folded as a binary counter: level b holds the left child until bit b of t says the right one is here,
- * the left operand the one with the lower lanes.  18 registers of stack.  S0: shade_terms_s0. */
-template <bool S0>
-__device__ __forceinline__ f3 clear_lane_sum(const KShadow &ks, const uint2 *mixs, uint32_t nl, int32_t rng, int32_t att, int32_t refl,
-					     float att_offset, f3 p, f3 n, f3 dir, f3 kd, f3 ks3, float shin)
-{
-	const auto *EM = cptr(ks.emitters);
-	const uint32_t ne = ks.num_emitters;
-	const f3 zero = mk3(0.f, 0.f, 0.f);
-	f3 s0 = zero, s1 = zero, s2 = zero, s3 = zero, s4 = zero, s5 = zero, x = zero;
-	EmLane ev = { 0u, 0u, zero, zero, zero, zero, 0.f };
-	uint32_t ev_e = RTX_NONE;
-	for (uint32_t t = 0; t < WAVE; t++) {
-		const uint32_t l = __builtin_bitreverse32(t) >> 26;
-		x = zero;
-		for (uint32_t e = 0, start = 0; e < ne && start < nl; e++) {
-			const uint32_t end = start + EM[e].num_lights, lim = min(end, nl);
-			uint32_t idx = start <= l ? l : l + ((start - l + (WAVE - 1u)) & ~(WAVE - 1u));
-			if (idx < lim) {
-				if (ev_e != e) { /* once per render where there is one emitter */
-					ev = emitter_lanes(emitter_uni(ks.emitters + e));
-					ev_e = e;
-				}
-				DEmitter E = {};
-				E.type = ev.type;
-				E.num_lights = ev.num_lights;
-				E.radius = ev.radius;
-				st3(E.li, ev.li);
-				st3(E.p0, ev.p0);
-				st3(E.p1, ev.p1);
-				st3(E.p2, ev.p2);
-				const uint2 mw = mixs[e * RTX_CL_BLOCK];
-				const uint64_t mix = key_of(mw.x, mw.y);
-				for (; idx < lim; idx += WAVE) {
-					const uint32_t j = idx - start;
-					float u1 = 0.5f, u2 = 0.5f;
-					if (rng != RTX_RNG_CONST)
-						rtx_draw2_mixed(mix, j, &u1, &u2);
-					f3 ldir, li;
-					float ldist, dsq;
-					sample_ray(rng, E, j, u1, u2, p, ldir, ldist, dsq, li);
-					const float attf = sample_att_of(att, att_offset, ldist, dsq);
-					x = add3(x, S0 ? shade_terms_s0(att, n, kd, ks3, ldir, li, attf) :
-							 shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf));
-				}
-			}
-			start = end;
-		}
-		if (!(t & 1u)) {
-			s0 = x;
-			continue;
-		}
-		x = add3(s0, x);
-		if (!(t & 2u)) {
-			s1 = x;
-			continue;
-		}
-		x = add3(s1, x);
-		if (!(t & 4u)) {
-			s2 = x;
-			continue;
-		}
-		x = add3(s2, x);
-		if (!(t & 8u)) {
-			s3 = x;
-			continue;
-		}
-		x = add3(s3, x);
-		if (!(t & 16u)) {
-			s4 = x;
-			continue;
-		}
-		x = add3(s4, x);
-		if (!(t & 32u)) {
-			s5 = x;
-			continue;
-		}
-		x = add3(s5, x);
-	}
-	return x; /* t = 63 falls through every level: the root */
-}
-
-/* Lane i of the grid takes entry i of the clear list (RTX_C_CLPTS entries): its record and material per
- * lane, its draws' mix per emitter (kept in LDS, a slot per lane: 64-bit multiplies, not to be redone
- * per leaf), clear_lane_sum, and k_shadow's tail.  No loads in the loops but the emitter table's, through
- * the scalar cache.  The shininess-0 loop runs where every lane's point has shininess 0; else every lane
- * runs the generic one (the two give the same bits, RTX_OPT_SHADOW_SPEC).  One lane per wave counts the rays. */
-__global__ __launch_bounds__(RTX_CL_BLOCK) void k_shadow_clear(KShadow ks, const uint32_t *__restrict__ list)
-{
-	__shared__ uint2 mixs[8 * RTX_CL_BLOCK];
-	const uint32_t nc = uni((uint32_t)ks.ctr[RTX_C_CLPTS]);
-	const uint32_t i = blockIdx.x * RTX_CL_BLOCK + threadIdx.x;
-	if (uni(i) >= nc) /* the wave's first entry */
-		return;
-	const bool own = i < nc;
-	const uint32_t sid = list[own ? i : nc - 1u]; /* the lanes past the list redo its last point and store nothing */
-	const float4 *rec = ks.sp + (size_t)sid * SPREC;
-	const float4 q0 = ldg4(rec, 0), q1 = ldg4(rec, 16), q2 = ldg4(rec, 32), q3 = ldg4(rec, 48), q4 = ldg4(rec, 64), q5 = ldg4(rec, 80);
-	const f3 p = mk3(q0.x, q0.y, q0.z), n = mk3(q1.x, q1.y, q1.z), dir = mk3(q2.x, q2.y, q2.z), kd = mk3(q3.x, q3.y, q3.z);
-	const uint64_t key = key_of(__float_as_uint(q4.y), __float_as_uint(q4.z));
-	const DMaterial &mat = ks.mats[__float_as_uint(q3.w)];
-	const f3 ks3 = ld3(mat.ks);
-	const float shin = mat.shininess;
-	const uint32_t ne = min(ks.num_emitters, 8u);
-	const auto *EM = cptr(ks.emitters);
-	uint32_t nl = 0;
-	for (uint32_t e = 0; e < ne; e++) {
-		nl += EM[e].num_lights;
-		const uint64_t mix = rtx_draw_mix(key, e);
-		mixs[e * RTX_CL_BLOCK + threadIdx.x] = make_uint2((uint32_t)mix, (uint32_t)(mix >> 32));
-	}
-	const int32_t rng = ks.rng, att = ks.attenuation, refl = ks.reflection == RTX_BLINN ? RTX_BLINN : RTX_PHONG;
-	const float att_offset = in_vgpr(ks.att_offset);
-	const bool s0 = ks.spec && !ballot(!shin_zero(shin));
-	const f3 Ls = s0 ? clear_lane_sum<true>(ks, mixs + threadIdx.x, nl, rng, att, refl, att_offset, p, n, dir, kd, ks3, shin) :
-			   clear_lane_sum<false>(ks, mixs + threadIdx.x, nl, rng, att, refl, att_offset, p, n, dir, kd, ks3, shin);
-	if (own) {
-		const f3 c = mul3v(mk3(q0.w, q1.w, q2.w), Ls);
-		ks.contrib[sid] = make_float4(c.x, c.y, c.z, q5.x);
-	}
-	if (lane_id() == 0)
-		atomicAdd(&ks.ctr[RTX_C_CLRAYS], (unsigned long long)min(nc - i, (uint32_t)WAVE) * nl);
-}
-
-/* ------------------------------------------------------------------------ */
-/* k_shadow_rays: shadow_query on a caller's rays (rtx_trace_shadow_rays)   */
-/* ------------------------------------------------------------------------ */
-/* One 64-ray packet per wave and turn, ray i in lane i % 64 of packet i / 64: k_shadow's workgroup
- * (block size, LDS copies of the trees' top levels, lane stacks, argument block) around one call of
- * shadow_query per packet, every plane and every listed record tested, nothing culled.  A workgroup
- * takes packets blockIdx.x * RTX_SH_NW + wave, then strides by the grid, so the grid never exceeds
- * the one the lane-stack spill area was sized for.  Rays are two float4 (origin, dist | direction,
- * light object), results one (transmittance, blocked). */
-template <bool COUNT, int WALK, bool LA>
-__global__ __launch_bounds__(WAVE *RTX_SH_NW) void k_shadow_rays(KShadow ka, const float4 *__restrict__ rays, float4 *__restrict__ res,
-								 uint32_t n, unsigned long long *ctr)
-{
-	constexpr bool TOP = WALK == WALK_BVH2;
-	__shared__ uint4 top_q[TOP ? RTX_TOP_MAX : 1];
-	__shared__ uint32_t top_e[TOP ? RTX_TOP_MAX : 1];
-	__shared__ __attribute__((aligned(16))) uint32_t wstk[RTX_SH_NW][WALK == WALK_W8 ? RTX_W8_STACK + RTX_W8_TQ : 1][WAVE];
-	__shared__ KShadow ks_s;
-	__shared__ uint4 t8[WALK == WALK_W8 && RTX_W8_TOP ? RTX_W8_TOP_MAX * 4 : 1];
-	const uint32_t ntop = TOP ? ka.ntop : 0u;
-	for (uint32_t i = threadIdx.x; i < ntop; i += WAVE * RTX_SH_NW) {
-		top_q[i] = ldg4u(ka.top + 4 * i);
-		top_e[i] = gptr(ka.top)[4 * ntop + i];
-	}
-	const uint32_t nt8 = (WALK == WALK_W8 && RTX_W8_TOP) ? min(ka.w8top, (uint32_t)RTX_W8_TOP_MAX) : 0u;
-	for (uint32_t i = threadIdx.x; i < 4 * nt8; i += WAVE * RTX_SH_NW)
-		t8[i] = ldg4u((const uint32_t *)ka.w8 + 4 * i);
-	const uint32_t wv = uni(threadIdx.x / WAVE);
-	if (threadIdx.x == 0)
-		ks_s = ka;
-	__syncthreads();
-	KShadow &ks = ks_s;
-	lds_u32 *stk = (lds_u32 *)&wstk[wv][0][LA ? 0u : lane_id()];
-	ShadowCount sc = {};
-	u64 n_live = 0, n_blocked = 0;
-	const uint32_t packets = (n + WAVE - 1) / WAVE;
-	for (uint32_t pk = blockIdx.x * RTX_SH_NW + wv; pk < packets; pk += gridDim.x * RTX_SH_NW) {
-		reread_barrier();
-		const size_t i = (size_t)pk * WAVE + lane_id();
-		const bool in = i < n;
-		float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, __uint_as_float(RTX_NONE));
-		if (in) {
-			r0 = rays[2 * i];
-			r1 = rays[2 * i + 1];
-		}
-		/* an idle lane: dist <= 0 or NaN, or a NaN direction component */
-		const bool act = in && r0.w > 0.f && r1.x == r1.x && r1.y == r1.y && r1.z == r1.z;
-		const f3 o = act ? mk3(r0.x, r0.y, r0.z) : mk3(0.f, 0.f, 0.f);
-		const f3 d = act ? mk3(r1.x, r1.y, r1.z) : mk3(0.f, 0.f, 1.f);
-		const float dist = act ? r0.w : 0.f;
-		/* far as k_trace marks a shade point (sp_far) */
-		const f3 of = uni(ks.tf.rotated) ? tf_point(ks.tf.r, ks.tf.c, o) : o;
-		const bool far = act && tf_far(of, ks.tf.cf, ks.tf.rad);
-		f3 li = mk3(1.f, 1.f, 1.f);
-		const QBvh Q = make_qbvh<WALK>(ks, top_q, top_e, stk, t8, wv);
-		const bool blocked = shadow_query<COUNT, WALK, LA>(Q, unip(ks.recs), unip(ks.mats), unip(ks.planes), uni(ks.num_planes),
-								 unip(ks.lin), uni(ks.num_lin), uni(ks.have_tree) != 0, ks.tf, act, far, o, d,
-								 dist, __float_as_uint(r1.w), li, sc);
-		reread_barrier();
-		if (in)
-			res[i] = blocked ? make_float4(0.f, 0.f, 0.f, __uint_as_float(1u)) : make_float4(li.x, li.y, li.z, 0.f);
-		n_live += popc64(ballot(act));
-		n_blocked += popc64(ballot(blocked));
-	}
-	if (lane_id() == 0) {
-		atomicAdd(&ctr[RTX_SQ_RAYS], n_live);
-		atomicAdd(&ctr[RTX_SQ_BLOCKED], n_blocked);
-		if (COUNT) {
-			atomicAdd(&ctr[RTX_SQ_FAR], sc.far);
-			atomicAdd(&ctr[RTX_SQ_BOXES], sc.boxes);
-			atomicAdd(&ctr[RTX_SQ_TRIS], sc.tris);
-			atomicAdd(&ctr[RTX_SQ_SPHERES], sc.sph);
-			atomicAdd(&ctr[RTX_SQ_STEPS], sc.steps);
-			atomicAdd(&ctr[RTX_SQ_UNIF], sc.unif);
-			atomicAdd(&ctr[RTX_SQ_LEAFR], sc.lrounds);
-			atomicAdd(&ctr[RTX_SQ_SPILL], sc.spills);
-		}
-	}
-}
-
-/* ------------------------------------------------------------------------ */
-/* known answers of the fast device functions k_shadow runs (rtx_kat.h)     */
-/* ------------------------------------------------------------------------ */
-__global__ void k_kat_shadow(int kind, uint32_t n, const float *__restrict__ in, float *__restrict__ out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const float *x = in + (size_t)i * rtx_kat_in_width[kind];
-	float *y = out + (size_t)i * rtx_kat_out_width[kind];
-	switch (kind) {
-	case RTX_KAT_ANY_TRI:
-		y[0] = any_tri(ld3(x + 6), ld3(x + 9), ld3(x + 12), ld3(x), ld3(x + 3), x[15], x[16]) ? 1.f : 0.f;
-		break;
-	case RTX_KAT_SPH_LIGHT_SH: {
-		DEmitter e;
-		e.type = RTX_SPHERE;
-		for (int k = 0; k < 3; k++)
-			e.p0[k] = x[k];
-		e.radius = x[3];
-		const f3 l = light_point_sh(e, ld3(x + 4), x[7], x[8]);
-		y[0] = l.x;
-		y[1] = l.y;
-		y[2] = l.z;
-	} break;
-	case RTX_KAT_SPEC_POW:
-		y[0] = fmaxf(0.f, sh_pow(x[0], x[1]));
-		break;
-	case RTX_KAT_PLANE_CLEAR:
-	case RTX_KAT_LIN_CLEAR: {
-		/* point_masks' predicates for one point, light and plane / record, beside the per-ray test of
-		 * one of k_shadow's own samples of that light */
-		const f3 p = ld3(x);
-		DEmitter e;
-		e.type = x[3] == 0.f ? RTX_SPHERE : RTX_TRIANGLE;
-		e.num_lights = 1;
-		for (int k = 0; k < 3; k++) {
-			e.p0[k] = x[4 + k];
-			e.p1[k] = x[7 + k];
-			e.p2[k] = x[10 + k];
-			e.li[k] = 1.f;
-		}
-		e.radius = x[13];
-		f3 lc, ldir, li;
-		float lr, ldist, dsq;
-		emitter_sphere(e, lc, lr);
-		const f3 ax0 = sub3(lc, p);
-		const float L = sqrtf(magsqr3(ax0));
-		const bool pk = kind == RTX_KAT_PLANE_CLEAR;
-		sample_ray(RTX_RNG_CONST, e, 0u, x[pk ? 19 : 26], x[pk ? 20 : 27], p, ldir, ldist, dsq, li);
-		bool clear, blocks;
-		if (pk) {
-			clear = plane_clear(ld3(x + 14), x[17], x[18], p, lc, lr, L);
-			blocks = plane_blocks(ld3(x + 14), x[17], p, ldir, x[18], ldist);
-		} else {
-			const bool sph = x[14] == 0.f;
-			float rs[4];
-			rtx_record_sphere(sph, x + 15, x + 18, x + 21, x[24], rs);
-			clear = L > 1.01f * lr && !cone_meets<true>(cone_of(p, lc, lr, ax0, L), p, make_float4(rs[0], rs[1], rs[2], rs[3]));
-			if (sph) {
-				float t = 0.f;
-				blocks = hit_sphere(ld3(x + 15), x[24], p, ldir, x[25], t) && t < ldist;
-			} else {
-				const f3 w0 = ld3(x + 15);
-				blocks = any_tri(w0, sub3(ld3(x + 18), w0), sub3(ld3(x + 21), w0), p, ldir, x[25], ldist);
-			}
-		}
-		y[0] = clear ? 1.f : 0.f;
-		y[1] = blocks ? 1.f : 0.f;
-		y[2] = ldir.x;
-		y[3] = ldir.y;
-		y[4] = ldir.z;
-		y[5] = ldist;
-	} break;
-	case RTX_KAT_DARK: {
-		/* dark_terms beside shade_terms for the sample's li and for li through one transparent
-		 * surface, the attenuation factor formed as light_sample forms it */
-		const f3 n = ld3(x), dir = ld3(x + 3), kd = ld3(x + 6), ks3 = ld3(x + 9), ldir = ld3(x + 13), li = ld3(x + 17), kt = ld3(x + 23);
-		const float shin = x[12], ldist = x[16];
-		const int32_t att = (int32_t)x[20], refl = (int32_t)x[22];
-		const float attf = sample_att_of(att, x[21], ldist, ldist * ldist);
-		const bool ok = fin3(li) && fabsf(kt.x) <= 1.f && fabsf(kt.y) <= 1.f && fabsf(kt.z) <= 1.f; /* scene_dark_ok */
-		const bool dark = ok && dark_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf, true);
-		const f3 t0 = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, li, attf);
-		const f3 t1 = shade_terms(att, refl, n, dir, kd, ks3, shin, ldir, mul3v(li, kt), attf);
-		y[0] = dark ? 1.f : 0.f;
-		y[1] = t0.x;
-		y[2] = t0.y;
-		y[3] = t0.z;
-		y[4] = t1.x;
-		y[5] = t1.y;
-		y[6] = t1.z;
-	} break;
-	case RTX_KAT_SPEC0: {
-		/* RTX_KAT_DARK's record through the shininess-0 forms (its shin is not read): what
-		 * dark_terms / shade_terms give for the same record with shin = +-0, bit for bit */
-		const f3 n = ld3(x), kd = ld3(x + 6), ks3 = ld3(x + 9), ldir = ld3(x + 13), li = ld3(x + 17), kt = ld3(x + 23);
-		const float ldist = x[16];
-		const int32_t att = (int32_t)x[20];
-		const float attf = sample_att_of(att, x[21], ldist, ldist * ldist);
-		const bool ok = fin3(li) && fabsf(kt.x) <= 1.f && fabsf(kt.y) <= 1.f && fabsf(kt.z) <= 1.f; /* scene_dark_ok */
-		const bool dark = ok && dark_terms_s0(att, n, kd, ks3, ldir, li, attf, true);
-		const f3 t0 = shade_terms_s0(att, n, kd, ks3, ldir, li, attf);
-		const f3 t1 = shade_terms_s0(att, n, kd, ks3, ldir, mul3v(li, kt), attf);
-		y[0] = dark ? 1.f : 0.f;
-		y[1] = t0.x;
-		y[2] = t0.y;
-		y[3] = t0.z;
-		y[4] = t1.x;
-		y[5] = t1.y;
-		y[6] = t1.z;
-	} break;
-	case RTX_KAT_BOX_Q: {
-		/* the walk's setup (shadow_query / shadow_walk) and its box test on the quantised box */
-		const f3 o = ld3(x), d = ld3(x + 3), qo = ld3(x + 12), qs = ld3(x + 15);
-		const uint4 nd = make_uint4(rtx_quantise(x[6], x[9], qo.x, qs.x), rtx_quantise(x[7], x[10], qo.y, qs.y),
-					    rtx_quantise(x[8], x[11], qo.z, qs.z), 0u);
-		const f3 inv = safe_inv_fast(d);
-		const f3 invq = mk3(inv.x * (1.f / qs.x), inv.y * (1.f / qs.y), inv.z * (1.f / qs.z));
-		const f3 oq = mk3((o.x - qo.x) * qs.x, (o.y - qo.y) * qs.y, (o.z - qo.z) * qs.z);
-		const f3 oi = mul3v(oq, invq);
-		const uint32_t oct = ((~__float_as_uint(inv.x)) >> 31) | (((~__float_as_uint(inv.y)) >> 31) << 1) |
-				     (((~__float_as_uint(inv.z)) >> 31) << 2);
-		bool ho = false;
-		switch (oct) {
-#define RTX_KATOCT(K)                                      \
-	case K:                                                \
-		ho = box_hit_q<K>(nd, oi, invq, x[18]);            \
-		break;
-			RTX_KATOCT(0) RTX_KATOCT(1) RTX_KATOCT(2) RTX_KATOCT(3) RTX_KATOCT(4) RTX_KATOCT(5) RTX_KATOCT(6)
-			RTX_KATOCT(7)
-#undef RTX_KATOCT
-		}
-		y[0] = box_hit_q<8>(nd, oi, invq, x[18]) ? 1.f : 0.f;
-		y[1] = ho ? 1.f : 0.f;
-	} break;
-	case RTX_KAT_BOX_Q8: {
-		/* the 8-wide walk's setup and child test on the box quantised to 16 bits, then to 8 bits in
-		 * the node frame (org, e) given by the record, exactly as rtx_wide8_build does */
-		const f3 o = ld3(x), d = ld3(x + 3), qo = ld3(x + 12), qs = ld3(x + 15);
-		uint32_t w[16];
-		for (int k = 0; k < 16; k++)
-			w[k] = 0;
-		const uint32_t org[3] = { (uint32_t)x[19], (uint32_t)x[20], (uint32_t)x[21] };
-		const uint32_t ex[3] = { (uint32_t)x[22], (uint32_t)x[23], (uint32_t)x[24] };
-		w[0] = org[0] | (org[1] << 16);
-		w[1] = org[2] | (ex[0] << 16) | (ex[1] << 20) | (ex[2] << 24);
-		w[3] = 1u;
-		for (int a = 0; a < 3; a++) {
-			const uint32_t q8 = rtx_quantise8(rtx_quantise(x[6 + a], x[9 + a], x[12 + a], x[15 + a]), org[a], ex[a]);
-			w[4 + 4 * a] = (q8 & 0xFFu) | 0xFFFFFF00u; /* slot 0 the box, slots 1..7 empty */
-			w[5 + 4 * a] = 0xFFFFFFFFu;
-			w[6 + 4 * a] = q8 >> 8;
-			w[7 + 4 * a] = 0u;
-		}
-		const f3 inv = safe_inv_fast(d);
-		const f3 invq = mk3(inv.x * (1.f / qs.x), inv.y * (1.f / qs.y), inv.z * (1.f / qs.z));
-		const f3 oq = mk3((o.x - qo.x) * qs.x, (o.y - qo.y) * qs.y, (o.z - qo.z) * qs.z);
-		const f3 oi = mul3v(oq, invq);
-		const uint32_t oct = ((~__float_as_uint(inv.x)) >> 31) | (((~__float_as_uint(inv.y)) >> 31) << 1) |
-				     (((~__float_as_uint(inv.z)) >> 31) << 2);
-		f3 sc, bc;
-		w8_frame(w, invq, oi, sc, bc);
-		uint32_t ho = 0;
-		switch (oct) {
-#define RTX_KATOCT8(K)                                                        \
-	case K:                                                                   \
-		ho = w8_hits<K, (~(uint32_t)K & 7u)>(w, sc, bc, x[18]);               \
-		ho = ho == (1u << (~(uint32_t)K & 7u)) ? 1u : ho ? 2u : 0u;           \
-		break;
-			RTX_KATOCT8(0) RTX_KATOCT8(1) RTX_KATOCT8(2) RTX_KATOCT8(3) RTX_KATOCT8(4) RTX_KATOCT8(5) RTX_KATOCT8(6)
-			RTX_KATOCT8(7)
-#undef RTX_KATOCT8
-		}
-		const uint32_t hg = w8_hits<8, 0u>(w, sc, bc, x[18]);
-		/* 1 = slot 0 hit alone; 2 would flag an empty slot hit (never expected) */
-		y[0] = hg == 1u ? 1.f : hg ? 2.f : 0.f;
-		y[1] = (float)ho;
-	} break;
-	}
-}
-
-/* RTX_KAT_ORDER: order_begin for one shade point and one emitter of nl lights, one wave per record.
- * The point's record, the emitter, the material, the masks and the wave's slice live in the output
- * record's tail (rtx_kat.h); k_kat_order_fill writes them first, in a launch of its own, as
- * order_begin reads them through the scalar cache */
-static_assert(sizeof(DEmitter) <= 256 && sizeof(DMaterial) <= 256, "the KAT record's emitter and material slots");
-__global__ void k_kat_order_fill(uint32_t n, const float *__restrict__ in, float *__restrict__ out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const float *x = in + (size_t)i * rtx_kat_in_width[RTX_KAT_ORDER];
-	float *y = out + (size_t)i * rtx_kat_out_width[RTX_KAT_ORDER];
-	float4 *rec = (float4 *)(y + RTX_KAT_ORDER_REC);
-	DEmitter *em = (DEmitter *)(y + RTX_KAT_ORDER_REC + 24);
-	DMaterial *mat = (DMaterial *)(y + RTX_KAT_ORDER_REC + 24 + 64);
-	uint32_t *cm = (uint32_t *)y + RTX_KAT_ORDER_REC + 24 + 128;
-	const uint32_t nl = (uint32_t)x[26];
-	DEmitter e;
-	memset(&e, 0, sizeof(e));
-	e.obj = 1u;
-	e.type = x[16] == 0.f ? RTX_SPHERE : RTX_TRIANGLE;
-	e.num_lights = nl;
-	for (int k = 0; k < 3; k++) {
-		e.li[k] = 1.f;
-		e.p0[k] = x[17 + k];
-		e.p1[k] = x[20 + k];
-		e.p2[k] = x[23 + k];
-		e.e1[k] = e.p1[k] - e.p0[k];
-		e.e2[k] = e.p2[k] - e.p0[k];
-	}
-	e.radius = x[29];
-	*em = e;
-	DMaterial m;
-	memset(&m, 0, sizeof(m));
-	for (int k = 0; k < 3; k++)
-		m.ks[k] = x[12 + k];
-	m.shininess = x[15];
-	*mat = m;
-	rec[0] = make_float4(x[0], x[1], x[2], 1.f);
-	rec[1] = make_float4(x[3], x[4], x[5], 1.f);
-	rec[2] = make_float4(x[6], x[7], x[8], 1.f);
-	rec[3] = make_float4(x[9], x[10], x[11], __uint_as_float(0u));
-	rec[4] = make_float4(__uint_as_float(0u), __uint_as_float((uint32_t)x[27]), __uint_as_float((uint32_t)x[28]), __uint_as_float(nl));
-	rec[5] = make_float4(0.f, 0.f, 0.f, 0.f);
-	for (int k = 0; k < 8; k++)
-		cm[k] = 0u;
-}
-__global__ __launch_bounds__(WAVE) void k_kat_order(uint32_t n, const float *__restrict__ in, float *__restrict__ out)
-{
-	const float *x = in + (size_t)blockIdx.x * rtx_kat_in_width[RTX_KAT_ORDER];
-	float *y = out + (size_t)blockIdx.x * rtx_kat_out_width[RTX_KAT_ORDER];
-	uint32_t *yu = (uint32_t *)y;
-	const float4 *rec = (const float4 *)(y + RTX_KAT_ORDER_REC);
-	const DEmitter *em = (const DEmitter *)(y + RTX_KAT_ORDER_REC + 24);
-	const DMaterial *mat = (const DMaterial *)(y + RTX_KAT_ORDER_REC + 24 + 64);
-	uint32_t *cm = yu + RTX_KAT_ORDER_REC + 24 + 128, *ob = cm + 8;
-	const uint32_t nl = (uint32_t)x[26];
-	__shared__ KShadow ks;
-	if (threadIdx.x == 0) {
-		memset(&ks, 0, sizeof(ks));
-		ks.emitters = em;
-		ks.num_emitters = 1u;
-		ks.mats = mat;
-		ks.rng = RTX_RNG_COUNTER;
-		ks.reflection = (int32_t)x[33];
-		ks.attenuation = (int32_t)x[34];
-		ks.att_offset = x[35];
-		ks.dark = x[36] != 0.f ? 1u : 0u;
-		ks.spec = 1u; /* the default, as the product's key pass runs */
-		for (int k = 0; k < 3; k++)
-			ks.tf.c[k] = x[30 + k];
-	}
-	__syncthreads();
-	ShadowCount sc = {};
-	const uint32_t st = order_begin<false, WALK_W8>(ks, rec, nl, 0u, cm, ob, sc);
-	if (threadIdx.x == 0) {
-		y[0] = st ? (float)(st & 0x7ffu) : 0.f;
-		y[1] = st ? (float)((st >> 16) & 31u) : 0.f;
-		y[2] = 0.f;
-		y[3] = 0.f;
-	}
-	/* every sample's bucket and x again, from the function order_begin takes them from */
-	const DEmitter Eu = emitter_uni(em);
-	const f3 p = ld3(x);
-	f3 lc;
-	float lr;
-	emitter_sphere(Eu, lc, lr);
-	const f3 b = order_dir(p, lc, mk3(x[30], x[31], x[32]));
-	const float ilr = lr > 0.f ? 1.f / lr : 0.f;
-	for (uint32_t j = threadIdx.x; j < RTX_ORD_CAP; j += WAVE) {
-		bool dark;
-		float xv = 0.f;
-		const uint32_t bk = order_key(ks, rec, Eu, 0u, j, (uint32_t)x[27], (uint32_t)x[28], p, b, ilr, ks.dark != 0, j < nl, dark, &xv);
-		y[4 + j] = st && j < (st & 0x7ffu) ? (float)ob[j] : -1.f;
-		y[4 + RTX_ORD_CAP + j] = (float)bk;
-		y[4 + 2 * RTX_ORD_CAP + j] = j < nl ? xv : 0.f;
-	}
-}
-
-/* the 8-wide BVH's leaf entries: the primitive records they stand for (leafmap[i] = primitive
- * index, RTX_NONE for node entries and holes) */
-__global__ void k_w8_fill(const DPrim *__restrict__ prims, const DMaterial *__restrict__ mats, const uint32_t *__restrict__ leafmap,
-			  uint32_t n, DW8 *__restrict__ out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= 4 * n)
-		return;
-	const uint32_t e = i >> 2, p = leafmap[e];
-	if (p == RTX_NONE)
-		return;
-	float4 v = ldg4((const char *)(prims + p), 16 * (i & 3));
-	if ((i & 3) == 3) { /* the walks' copy: the material's kt in place of the normal, the record index */
-		const DMaterial &m = mats[__float_as_uint(prims[p].c[3]) & RTX_META_MAT];
-		v = make_float4(m.kt[0], m.kt[1], m.kt[2], __uint_as_float(p));
-	}
-	((float4 *)(out + e))[i & 3] = v;
-}
-
-extern "C" hipError_t rtx_launch_w8_fill(const DPrim *prims, const DMaterial *mats, const uint32_t *leafmap, uint32_t n, DW8 *out,
-					  hipStream_t stream)
-{
-	if (!n)
-		return hipSuccess;
-	hipLaunchKernelGGL(k_w8_fill, dim3((4 * n + 255) / 256), dim3(256), 0, stream, prims, mats, leafmap, n, out);
-	return hipGetLastError();
-}
-
-extern "C" hipError_t rtx_launch_kat_shadow(int kind, uint32_t n, const float *in, float *out, hipStream_t stream)
-{
-	if (kind < RTX_KAT_FIRST_SHADOW || kind >= RTX_KAT_NKINDS)
-		return hipErrorInvalidValue;
-	if (kind == RTX_KAT_ORDER) {
-		hipLaunchKernelGGL(k_kat_order_fill, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, n, in, out);
-		hipLaunchKernelGGL(k_kat_order, dim3(n), dim3(WAVE), 0, stream, n, in, out);
-	} else
-		hipLaunchKernelGGL(k_kat_shadow, dim3((n + 255) / 256), dim3(256), 0, stream, kind, n, in, out);
-	return hipGetLastError();
-}
-
-/* ------------------------------------------------------------------------ */
-/* launcher (declared in rtx_launch.h)                                      */
-/* ------------------------------------------------------------------------ */
-template <bool C, int O, int W, int P> static hipError_t shadow_slots(uint32_t cus, uint32_t *slots)
-{
-	int per_cu = 0;
-	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_shadow<C, O, W, P>),
-								   WAVE * RTX_SH_NW, 0);
-	*slots = per_cu > 0 && cus > 0 ? (uint32_t)per_cu * cus : 1024u;
-	return e;
-}
-
-/* the persistent grid: as many workgroups as are resident on the device at once (no more than
- * the work needs); the waves then share the shade points through RTX_C_SPQUEUE */
-template <bool C, int O, int W, int P>
-static hipError_t launch_shadow_p(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream, uint32_t max_wgs)
-{
-	uint32_t slots = 0;
-	hipError_t e = shadow_slots<C, O, W, P>(cus, &slots);
-	if (e != hipSuccess)
-		return e;
-	const uint32_t need = (nw + RTX_SH_NW - 1) / RTX_SH_NW;
-	if (ka.ord && max_wgs && slots > max_wgs) /* no more workgroups than the order buffer has slices for */
-		slots = max_wgs;
-	hipLaunchKernelGGL((k_shadow<C, O, W, P>), dim3(need < slots ? need : slots), dim3(WAVE * RTX_SH_NW), 0, stream, ka);
-	return hipGetLastError();
-}
-/* the counting instances keep both layouts in one kernel; the product picks the layout's own */
-template <bool C, int O, int W>
-static hipError_t launch_shadow(const KShadow &ka, uint32_t nw, uint32_t cus, hipStream_t stream, uint32_t max_wgs)
-{
-	if constexpr (C) {
-		return launch_shadow_p<C, O, W, 0>(ka, nw, cus, stream, max_wgs);
-	} else {
-		if (ka.slot_b == WAVE)
-			return ka.ord ? launch_shadow_p<C, O, W, 5>(ka, nw, cus, stream, max_wgs) :
-			       ka.dark ? launch_shadow_p<C, O, W, 4>(ka, nw, cus, stream, max_wgs) : launch_shadow_p<C, O, W, 1>(ka, nw, cus, stream, max_wgs);
-		if (W == WALK_W8 && ka.cull_slots && ka.num_cull)
-			return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 3>(ka, nw, cus, stream, max_wgs);
-		return launch_shadow_p<C, O == RTX_SHADOW_OCC_DEFAULT ? RTX_SHADOW_OCC_SLOT : O, W, 2>(ka, nw, cus, stream, max_wgs);
-	}
-}
-
-template <int W> static hipError_t launch_walk(const KShadow &ka, uint32_t nw, uint32_t cus, int count, hipStream_t stream, uint32_t max_wgs)
-{
-	if (count)
-		return launch_shadow<true, 1, W>(ka, nw, cus, stream, max_wgs);
-#if RTX_MEASURE
-	/* occupancy variant (measurement builds): RTX_SHADOW_OCC = 1 (the compiler's choice) */
-	const char *env = getenv("RTX_SHADOW_OCC");
-	if (env && atoi(env) != RTX_SHADOW_OCC_DEFAULT)
-		return launch_shadow<false, 1, W>(ka, nw, cus, stream, max_wgs);
-#endif
-	return launch_shadow<false, RTX_SHADOW_OCC_DEFAULT, W>(ka, nw, cus, stream, max_wgs);
-}
-
-/* the walk k_shadow runs for a scene: the 8-wide BVH when built, else the threaded BVH2 */
-static int walk_of(const DScene *S) { return S->w8 ? WALK_W8 : WALK_BVH2; }
-
-/* grid lanes of the largest k_shadow launch on `cus` CUs (sizes the 8-wide walk's spill area) */
-extern "C" hipError_t rtx_shadow_grid_lanes(uint32_t cus, uint32_t *lanes)
-{
-	uint32_t a = 0, b = 0, a2 = 0;
-	hipError_t e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 1>(cus, &a);
-	if (e == hipSuccess) {
-		uint32_t a4 = 0;
-		e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 4>(cus, &a4);
-		a = a > a4 ? a : a4;
-	}
-	if (e == hipSuccess) {
-		uint32_t a5 = 0;
-		e = shadow_slots<false, RTX_SHADOW_OCC_DEFAULT, WALK_W8, 5>(cus, &a5);
-		a = a > a5 ? a : a5;
-	}
-	if (e == hipSuccess)
-		e = shadow_slots<false, RTX_SHADOW_OCC_SLOT, WALK_W8, 2>(cus, &a2);
-	if (e == hipSuccess) {
-		uint32_t a3 = 0;
-		e = shadow_slots<false, RTX_SHADOW_OCC_SLOT, WALK_W8, 3>(cus, &a3);
-		a2 = a2 > a3 ? a2 : a3;
-	}
-	a = a > a2 ? a : a2;
-	if (e == hipSuccess)
-		e = shadow_slots<true, 1, WALK_W8, 0>(cus, &b);
-#if RTX_MEASURE
-	uint32_t c = 0, c2 = 0;
-	if (e == hipSuccess)
-		e = shadow_slots<false, 1, WALK_W8, 1>(cus, &c);
-	if (e == hipSuccess)
-		e = shadow_slots<false, 1, WALK_W8, 2>(cus, &c2);
-	c = c > c2 ? c : c2;
-	b = b > c ? b : c;
-#endif
-	*lanes = (a > b ? a : b) * WAVE * RTX_SH_NW;
-	return e;
-}
-
-/* the scene's part of k_shadow's arguments (trees, frames, records, the walk's LDS stack size): what
- * rtx_launch_shadow and rtx_launch_shadow_rays share.  Checks what the kernels rely on: the top levels
- * fit their LDS copy, the lane stack its LDS entries, and a deep 8-wide tree has a spill area for
- * the largest grid */
-static hipError_t shadow_scene_args(const DScene *S, uint32_t cus, KShadow &ka)
-{
-	if (S->num_top > RTX_TOP_MAX)
-		return hipErrorInvalidValue;
-	const int walk = walk_of(S);
-	if (walk == WALK_W8 && (S->w8lstk < 1 || S->w8lstk > RTX_W8_STACK))
-		return hipErrorInvalidValue;
-	if (walk == WALK_W8 && S->w8depth > S->w8lstk + 1) {
-		/* deep trees spill lane-stack entries to HBM: the area must cover this launch's grid */
-		uint32_t lanes = 0;
-		hipError_t e = rtx_shadow_grid_lanes(cus, &lanes);
-		if (e != hipSuccess)
-			return e;
-		if (!S->w8spill || S->w8spill_lanes < lanes)
-			return hipErrorInvalidValue;
-	}
-	ka.recs = (const char *)S->nodes;
-	ka.qnodes = S->qnodes;
-	ka.top = S->top;
-	ka.ntop = S->num_top;
-	ka.tf = S->tf;
-	for (int a = 0; a < 3; a++) {
-		ka.qo[a] = S->qo[a];
-		ka.qs[a] = S->qs[a];
-		ka.qsi[a] = 1.f / S->qs[a];
-	}
-	ka.mats = S->mats;
-	ka.planes = S->planes;
-	ka.emitters = S->emitters;
-	ka.have_tree = S->root_ref != RTX_EMPTY_REF && !S->lin && (S->w8 || S->qnodes); /* the walk of walk_of(S) has its tree */
-	ka.num_planes = S->num_planes;
-	ka.num_emitters = S->num_emitters;
-	ka.w8 = S->w8;
-	ka.w8s = S->w8s;
-	ka.w8spill = S->w8spill;
-	ka.w8lstk = S->w8lstk;
-	ka.w8top = S->w8top;
-	ka.w8sph = S->w8sph;
-	ka.lin = S->lin; /* a tiny scene: every bounded object, no walk */
-	ka.cull = (const float4 *)S->cull;
-	ka.num_cull = (walk == WALK_W8 && S->cull) ? S->num_cull : 0u;
-	ka.cull_slots = S->cull_slots;
-	ka.point = S->point;
-	/* only where shadow rays walk a tree: against a handful of listed objects the predicate costs
-	 * more than the tests it saves (scene3, RTX_WALK_LINEAR: 59.9 -> 61.7 ms per frame with it) */
-	ka.dark = (S->dark && S->dark_ok && ka.have_tree) ? 1u : 0u;
-	ka.spec = S->spec;
-	ka.num_lin = S->lin ? S->num_lin : 0u;
-	if (walk == WALK_W8) { /* the 8-wide tree's own frame; the emitters it leaves out are tested linearly */
-		for (int a = 0; a < 3; a++) {
-			ka.qo[a] = S->w8qo[a];
-			ka.qs[a] = S->w8qs[a];
-			ka.qsi[a] = 1.f / S->w8qs[a];
-		}
-		ka.lin = S->emitters;
-		ka.num_lin = S->w8noemit ? S->num_emitters : 0u;
-	}
-	/* the listed records' bounding spheres, when they are those of the records this walk lists */
-	ka.lsph = (const float4 *)S->lsph;
-	ka.num_lsph = (S->lsph && S->num_lsph == ka.num_lin) ? S->num_lsph : 0u;
-	return hipSuccess;
-}
-
-extern "C" hipError_t rtx_launch_shadow(const DScene *S, const DParams *P, const float4 *sp, const uint32_t *perm,
-					uint32_t n_sp, uint32_t per_wave, uint32_t slot_b, float4 *contrib,
-					unsigned long long *ctr, int count, uint32_t cus, hipStream_t stream, uint32_t *pmask,
-					int *premasked, uint32_t *clbuf, int *clearlane)
-{
-	if (premasked)
-		*premasked = 0;
-	if (clearlane)
-		*clearlane = 0;
-	const uint32_t nw = per_wave ? (n_sp + per_wave - 1) / per_wave : 0u;
-	if (!slot_b || (slot_b & (slot_b - 1)) || slot_b > WAVE || !per_wave || per_wave > WAVE)
-		return hipErrorInvalidValue;
-	if (!nw)
-		return hipSuccess;
-	KShadow ka;
-	hipError_t e = shadow_scene_args(S, cus, ka);
-	if (e != hipSuccess)
-		return e;
-	ka.sp = sp;
-	ka.perm = perm;
-	ka.contrib = contrib;
-	ka.ctr = ctr;
-	ka.n_sp = n_sp;
-	ka.per_wave = per_wave;
-	ka.slot_b = slot_b;
-	ka.slot_lg = (uint32_t)__builtin_ctz(slot_b);
-	ka.rng = P->rng;
-	ka.attenuation = P->attenuation;
-	ka.reflection = P->reflection;
-	ka.att_offset = P->att_offset;
-	/* the points' masks ahead of the kernel (k_point_masks, pmask: a word per record of the chunk): where
-	 * k_shadow would form them, one point per wave (the wave-uniform packets), and a byte per mask holds
-	 * the emitters; else k_shadow forms them itself */
-	/* the sample order: where shadow rays walk a tree, with the waves' slices for this launch's grid */
-	ka.ord = nullptr;
-	uint32_t ord_wgs = 0; /* the workgroups its buffer has slices for: the grid is held to them */
-	if (S->order && slot_b == WAVE && ka.have_tree) {
-		if (!S->ordbuf || S->ordbuf_waves < RTX_SH_NW)
-			return hipErrorInvalidValue;
-		ka.ord = S->ordbuf;
-		ord_wgs = S->ordbuf_waves / RTX_SH_NW;
-	}
-	ka.pm = nullptr;
-	if (pmask && slot_b == WAVE && ka.num_emitters <= 8u && (ka.num_cull || ka.point)) {
-		hipLaunchKernelGGL(k_point_masks, dim3((n_sp + RTX_PM_BLOCK - 1) / RTX_PM_BLOCK), dim3(RTX_PM_BLOCK), 0, stream, ka, pmask);
-		e = hipGetLastError();
-		if (e != hipSuccess)
-			return e;
-		ka.pm = pmask;
-		if (premasked)
-			*premasked = 1;
-	}
-	/* RTX_OPT_SHADOW_CLEARLANE: the wave-uniform packets of a render that does not count, their masks formed
-	 * above and RTX_OPT_SHADOW_POINT on.  clbuf (rtx_clearlane_words(n_sp) words) takes the processing order
-	 * split into the clear list and the rest, then the partition's prefix sums; k_clear_scan leaves the
-	 * clear list's length in k_shadow's queue head, so k_shadow, handed the whole array and n_sp as they
-	 * are, takes the rest list alone, and k_shadow_clear takes the clear list.  Nothing is read back here. */
-	if (S->clearlane && clbuf && ka.pm && ka.point && slot_b == WAVE && !count) {
-		const uint32_t nb = (n_sp + RTX_CL_ITEMS - 1) / RTX_CL_ITEMS;
-		uint32_t *off = clbuf + n_sp;
-		hipLaunchKernelGGL(k_clear_count, dim3(nb), dim3(RTX_CL_BLOCK), 0, stream, ka, off);
-		hipLaunchKernelGGL(k_clear_scan, dim3(1), dim3(1024), 0, stream, off, nb, ctr);
-		hipLaunchKernelGGL(k_clear_scatter, dim3(nb), dim3(RTX_CL_BLOCK), 0, stream, ka, (const uint32_t *)off, clbuf);
-		hipLaunchKernelGGL(k_shadow_clear, dim3((n_sp + RTX_CL_BLOCK - 1) / RTX_CL_BLOCK), dim3(RTX_CL_BLOCK), 0, stream, ka,
-				   (const uint32_t *)clbuf);
-		e = hipGetLastError();
-		if (e != hipSuccess)
-			return e;
-		ka.perm = clbuf;
-		if (clearlane)
-			*clearlane = 1;
-	}
-	if (walk_of(S) == WALK_W8)
-		return launch_walk<WALK_W8>(ka, nw, cus, count, stream, ord_wgs);
-	return launch_walk<WALK_BVH2>(ka, nw, cus, count, stream, ord_wgs);
-}
-
-/* the words of rtx_launch_shadow's clbuf for a chunk of n_sp shade points */
-extern "C" size_t rtx_clearlane_words(uint32_t n_sp)
-{
-	return (size_t)n_sp + (n_sp + RTX_CL_ITEMS - 1) / RTX_CL_ITEMS + 1;
-}
-
-/* n caller's shadow rays through shadow_query (k_shadow_rays): the instance follows the scene as
- * rtx_launch_shadow's does (walk_of; a tiny scene's list has no tree), `slots` picks the lane-slot
- * kernels' stack addressing (LA), `count` the counting instance.  ctr: RTX_SQ_N zeroed counters. */
-template <bool C, int W, bool LA>
-static hipError_t launch_shadow_rays(const KShadow &ka, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
-				     uint32_t cus, uint32_t spill_lanes, hipStream_t stream)
-{
-	int per_cu = 0;
-	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_shadow_rays<C, W, LA>),
-								   WAVE * RTX_SH_NW, 0);
-	if (e != hipSuccess)
-		return e;
-	uint32_t grid = per_cu > 0 && cus > 0 ? (uint32_t)per_cu * cus : 1024u;
-	if (spill_lanes) /* no more workgroups than the spill area has lanes for (w8_spill_at) */
-		grid = grid < spill_lanes / (WAVE * RTX_SH_NW) ? grid : spill_lanes / (WAVE * RTX_SH_NW);
-	const uint32_t need = ((n + WAVE - 1) / WAVE + RTX_SH_NW - 1) / RTX_SH_NW;
-	grid = grid < need ? grid : need;
-	if (!grid)
-		return hipErrorInvalidValue;
-	hipLaunchKernelGGL((k_shadow_rays<C, W, LA>), dim3(grid), dim3(WAVE * RTX_SH_NW), 0, stream, ka, rays, res, n, ctr);
-	return hipGetLastError();
-}
-
-extern "C" hipError_t rtx_launch_shadow_rays(const DScene *S, const float4 *rays, float4 *res, uint32_t n, unsigned long long *ctr,
-					     int slots, int count, uint32_t cus, hipStream_t stream)
-{
-	if (!n)
-		return hipSuccess;
-	KShadow ka{};
-	hipError_t e = shadow_scene_args(S, cus, ka);
-	if (e != hipSuccess)
-		return e;
-	const uint32_t spill = (walk_of(S) == WALK_W8 && S->w8depth > S->w8lstk + 1) ? S->w8spill_lanes : 0u;
-#define RTX_SR(C, W, LA) launch_shadow_rays<C, W, LA>(ka, rays, res, n, ctr, cus, spill, stream)
-	if (walk_of(S) == WALK_W8) {
-		if (count)
-			return slots ? RTX_SR(true, WALK_W8, true) : RTX_SR(true, WALK_W8, false);
-		return slots ? RTX_SR(false, WALK_W8, true) : RTX_SR(false, WALK_W8, false);
-	}
-	/* the BVH2 walk and the listed objects keep no lane stack: LA changes nothing there */
-	return count ? RTX_SR(true, WALK_BVH2, false) : RTX_SR(false, WALK_BVH2, false);
-#undef RTX_SR
-}
-
-/* the code object of this file on the current device, loaded now (rtx_open) rather than at the
- * first launch inside an upload or a render */
-extern "C" __attribute__((visibility("hidden"))) hipError_t rtx_load_shadow(void)
-{
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *)k_w8_fill);
-}
+/* Nothing below is compiled into a k_shadow instance.  Each part relies on the code above and on the
+ * parts before it, and is included here only. */
+#include "rtx_shadow_premask.h"   /* k_point_masks: the per-point masks ahead of k_shadow */
+#include "rtx_shadow_clearlane.h" /* k_clear_count / _scan / _scatter, k_shadow_clear: the all-clear points, one per lane */
+#include "rtx_shadow_rays.h"      /* k_shadow_rays: shadow_query on a caller's rays */
+#include "rtx_shadow_kat.h"       /* the known-answer-test kernels */
+#include "rtx_shadow_launch.h"    /* k_w8_fill and the host launch code (rtx_launch.h) */

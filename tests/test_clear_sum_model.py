@@ -1,4 +1,4 @@
-"""The order k_shadow_clear adds a point's light samples in (rtx_shadow.hip clear_lane_sum) against the
+"""The order k_shadow_clear adds a point's light samples in (rtx_shadow_clearlane.h clear_lane_sum) against the
 order k_shadow does, as numpy float32 models, bit for bit.
 
 k_shadow: lane l of the wave adds samples l, l + 64, l + 128, ... below nl to a sum that starts at +0, then

@@ -1,4 +1,4 @@
-"""RTX_OPT_SHADOW_CLEARLANE (rtx.h; rtx_shadow.hip k_clear_count / k_clear_scan / k_clear_scatter and
+"""RTX_OPT_SHADOW_CLEARLANE (rtx.h; rtx_shadow_clearlane.h k_clear_count / k_clear_scan / k_clear_scatter and
 k_shadow_clear): the all-clear shade points that lie on no emitter are split off the processing order and
 shaded one per lane, their samples in sequence, summed in the order of k_shadow's 64-lane reduction.
 

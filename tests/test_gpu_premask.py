@@ -1,4 +1,4 @@
-"""The per-point masks formed ahead of k_shadow (rtx.h RTX_OPT_SHADOW_PREMASK, rtx_shadow.hip
+"""The per-point masks formed ahead of k_shadow (rtx.h RTX_OPT_SHADOW_PREMASK, rtx_shadow_premask.h
 k_point_masks): where k_shadow would form a shade point's cone, plane and listed-object masks with a
 whole wave (point_masks), a kernel of its own forms them first, one point per lane, through the same
 functions, and k_shadow reads one word per point.  The masks are the same, so with the option on and
