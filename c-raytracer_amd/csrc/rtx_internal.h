@@ -2,7 +2,7 @@
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
  * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
- * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_upsample.cpp (feature-guided upsampling), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
+ * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_upsample.cpp (feature-guided upsampling), rtx_temporal.cpp (temporal accumulation), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
  */
@@ -242,6 +242,21 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<uint32_t> d_up_list;       /* the refinement list */
 	DevBuf<unsigned long long> d_up_out; /* its length, and the pixels below the threshold */
 	rtx_upsample_stats up_stats{};
+	/* temporal accumulation (rtx_temporal*, rtx_render_temporal*): grow-only scratch of its own, rtx_temporal.hip */
+	struct TemporalSet {              /* a frame as the pipeline keeps it: the current one, then the history */
+		DevBuf<float> rgb, var, len;
+		DevBuf<float4> feat;
+	};
+	TemporalSet tp_set[2];            /* the pipeline's two sets, used in turn */
+	TemporalSet tp_host[2];           /* the host-buffer call's device copies of the current frame and of the history */
+	DevBuf<float> d_tp_conf;          /* the host-buffer call's device copy of the confidence */
+	DevBuf<unsigned long long> d_tp_ctr; /* k_temporal's RTX_TEMPORAL_CTR_WORDS words of statistics */
+	std::vector<unsigned long long> tp_ctr; /* ... read back */
+	uint32_t tp_hist = 0;             /* the set that holds the history */
+	bool tp_valid = false;            /* ... if there is one: cleared by rtx_temporal_reset and by an upload */
+	rtx_frame tp_frame{};             /* the history's frame */
+	uint32_t tp_frames = 0;           /* pipeline calls since the history was last forgotten */
+	rtx_temporal_stats tp_stats{};
 	/* rtx_set_option (include/rtx.h RTX_OPT_*) */
 	int opt_walk = RTX_WALK_AUTO;
 	uint32_t opt_leaf = 1;

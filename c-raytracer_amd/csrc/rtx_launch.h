@@ -169,6 +169,22 @@ RTX_HIDDEN hipError_t rtx_launch_upsample_tiles(uint32_t w, uint32_t h, float th
 						uint32_t *list, unsigned long long *out, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_upsample(void);
 
+/* rtx_temporal.hip: the temporal accumulation of rtx_temporal* and rtx_render_temporal*.  The previous frame's
+ * projection, formed on the host in double: q = m (P - o) row-major, u = q0 / q2 - 1, v = q1 / q2 */
+struct rtx_temporal_proj {
+	double m[9], o[3];
+};
+/* its statistics: RTX_TEMPORAL_CTR_SLOTS 64-bit sums, one per 128-byte line (live pixels | with-history pixels << 32) */
+#define RTX_TEMPORAL_CTR_SLOTS 256u
+#define RTX_TEMPORAL_CTR_STRIDE 16u
+#define RTX_TEMPORAL_CTR_WORDS (RTX_TEMPORAL_CTR_SLOTS * RTX_TEMPORAL_CTR_STRIDE)
+RTX_HIDDEN hipError_t rtx_launch_temporal(uint32_t w, uint32_t h, const rtx_temporal_params *tp, int same_frame,
+					  const rtx_temporal_proj *pr, const float *rgb, const float *var, const float4 *feat,
+					  const float *hist_rgb, const float *hist_var, const float *hist_len, const float4 *hist_feat,
+					  float *out_rgb, float *out_var, float *out_len, float *out_conf, unsigned long long *ctr,
+					  hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_temporal(void);
+
 }
 
 #endif

@@ -211,6 +211,7 @@ int rtx_upload_built(rtx_ctx *c, const HostScene &hs, DevTree *take)
 	c->have_scene = false;
 	c->sp_tile_seen = 0.0; /* the next render sizes its chunks from the static bound */
 	c->sp_tile_key = SpKey{};
+	c->tp_valid = false; /* rtx_render_temporal's history is of the scene before */
 	HIP_TRY(hipSetDevice(c->device));
 	if (!(hs.recs_on_device && c->d_nodes) && (rc = upload(c->d_nodes, hs.recs, c->stream)))
 		return rc;

@@ -89,10 +89,19 @@ class Scene:
                                                  os.fsencode(base_dir) if base_dir else None, C.byref(h)))
         return cls(h)
 
-    def frame(self, width, height):
+    def frame(self, width, height, camera=None):
+        """rtx_frame_setup of the scene's camera, or of `camera` (an abi.Camera: a moved copy of self.desc.camera)"""
         fr = Frame()
-        _check_scene(scene_lib().rtx_frame_setup(C.byref(self.desc.camera), width, height, C.byref(fr)))
+        cam = self.desc.camera if camera is None else camera
+        _check_scene(scene_lib().rtx_frame_setup(C.byref(cam), width, height, C.byref(fr)))
         return fr
+
+    def camera(self, move=(0.0, 0.0, 0.0)):
+        """a copy of the scene's camera, its position moved by `move` in world units (the orientation kept)"""
+        cam = abi.Camera.from_buffer_copy(self.desc.camera)
+        for i in range(3):
+            cam.position[i] += move[i]
+        return cam
 
     @property
     def num_objects(self):
@@ -628,6 +637,83 @@ class Renderer:
         _check(self.lib.rtx_get_upsample_stats(self._ctx, C.byref(s)))
         return s
 
+    def temporal(self, frame, rgb, variance, features, prev_frame=None, hist_rgb=None, hist_variance=None, hist_length=None,
+                 hist_features=None, conf=True, **params):
+        """rtx_temporal on host arrays: the current frame's rgb (h, w, 3), variance (the same shape, or None) and
+        features (h, w) accumulated into the history (prev_frame, hist_rgb, hist_variance, hist_length (h, w),
+        hist_features; all None: the first frame).  Returns (rgb, variance or None, length, conf); conf=False passes no
+        confidence buffer and returns None for it."""
+        p = temporal_params(**params)
+        w, h = frame.width, frame.height
+
+        def arr(a, dtype, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != shape:
+                raise ValueError(f"a buffer of shape {a.shape} where the frame needs {shape}")
+            return a
+
+        c, vc = arr(rgb, np.float32, (h, w, 3)), arr(variance, np.float32, (h, w, 3))
+        f = arr(features, abi.FEATURE_DTYPE, (h, w))
+        hc, vh = arr(hist_rgb, np.float32, (h, w, 3)), arr(hist_variance, np.float32, (h, w, 3))
+        hl, g = arr(hist_length, np.float32, (h, w)), arr(hist_features, abi.FEATURE_DTYPE, (h, w))
+        out = np.zeros((h, w, 3), np.float32)
+        out_var = np.zeros((h, w, 3), np.float32) if vc is not None else None
+        out_len = np.zeros((h, w), np.float32)
+        cf = np.zeros((h, w), np.float32) if conf else None
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        _check(self.lib.rtx_temporal(self._ctx, C.byref(p), C.byref(frame), ptr(c), ptr(vc), ptr(f),
+                                     C.byref(prev_frame) if prev_frame is not None else None, ptr(hc), ptr(vh), ptr(hl), ptr(g),
+                                     ptr(out), ptr(out_var), ptr(out_len), ptr(cf)))
+        return out, out_var, out_len, cf
+
+    def temporal_device(self, frame, d_rgb, d_variance, d_features, prev_frame, d_hist_rgb, d_hist_variance, d_hist_length,
+                        d_hist_features, d_out_rgb, d_out_variance, d_out_length, d_out_conf, stream=None, **params):
+        """rtx_temporal_device: device pointers (ints; the feature buffers 16-byte aligned) or None where the header
+        allows a NULL; stream: hipStream_t as int or None."""
+        p = temporal_params(**params)
+        vp = lambda d: C.c_void_p(d) if d else None  # noqa: E731
+        _check(self.lib.rtx_temporal_device(self._ctx, C.byref(p), C.byref(frame), vp(d_rgb), vp(d_variance), vp(d_features),
+                                            C.byref(prev_frame) if prev_frame is not None else None, vp(d_hist_rgb),
+                                            vp(d_hist_variance), vp(d_hist_length), vp(d_hist_features), vp(d_out_rgb),
+                                            vp(d_out_variance), vp(d_out_length), vp(d_out_conf), vp(stream)))
+
+    def render_temporal(self, frame, params, passes=1, jitter=False, aperture=0.0, focus=1.0, target_error=0.0, min_passes=2,
+                        **temporal):
+        """rtx_render_temporal on host arrays: render_passes of the frame, its features, and their accumulation into the
+        history this context keeps from its last call (vary params.seed from call to call).  Returns (rgb (h, w, 3),
+        z (h, w), variance (h, w, 3), length (h, w)); temporal_stats() describes the call."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        tp = temporal_params(**temporal)
+        w, h = frame.width, frame.height
+        rgb, z, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 3), np.float32)
+        length = np.zeros((h, w), np.float32)
+        _check(self.lib.rtx_render_temporal(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), C.byref(tp), rgb.ctypes.data,
+                                            z.ctypes.data, var.ctypes.data, length.ctypes.data))
+        return rgb, z, var, length
+
+    def render_temporal_device(self, frame, params, d_rgb, d_z, d_variance, d_length, stream=None, passes=1, jitter=False,
+                               aperture=0.0, focus=1.0, target_error=0.0, min_passes=2, **temporal):
+        """rtx_render_temporal_device: d_rgb / d_z / d_variance / d_length are device pointers (ints, 16-byte aligned)
+        or None; stream: hipStream_t as int or None."""
+        pp = pass_params(passes=passes, jitter=jitter, aperture=aperture, focus=focus, target_error=target_error,
+                         min_passes=min_passes)
+        tp = temporal_params(**temporal)
+        _check(self.lib.rtx_render_temporal_device(self._ctx, C.byref(frame), C.byref(params), C.byref(pp), C.byref(tp),
+                                                   *[C.c_void_p(d) if d else None for d in (d_rgb, d_z, d_variance, d_length)],
+                                                   C.c_void_p(stream) if stream else None))
+
+    def temporal_reset(self):
+        """rtx_temporal_reset: the next render_temporal is a first frame"""
+        _check(self.lib.rtx_temporal_reset(self._ctx))
+
+    def temporal_stats(self):
+        s = abi.TemporalStats()
+        _check(self.lib.rtx_get_temporal_stats(self._ctx, C.byref(s)))
+        return s
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)
@@ -679,6 +765,35 @@ def frame_scaled(frame, scale):
     out = Frame()
     _check(rtx_lib().rtx_frame_scaled(C.byref(frame), scale, C.byref(out)))
     return out
+
+
+def temporal_params(**params):
+    """rtx_temporal_params_default plus overrides (max_history, match_material, sigma_normal / _albedo / _plane)"""
+    p = abi.TemporalParams()
+    rtx_lib().rtx_temporal_params_default(C.byref(p))
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def frame_project(frame, points):
+    """rtx_frame_project (no device needed) of an (..., 3) array of world points, read as float32: (u, v, in_front)
+    arrays of the leading shape, u and v float64 in the frame's pixel coordinates, in_front bool"""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    if pts.shape[-1:] != (3,):
+        raise ValueError("points must have a last axis of 3")
+    flat = pts.reshape(-1, 3)
+    u, v = np.zeros(len(flat), np.float64), np.zeros(len(flat), np.float64)
+    front = np.zeros(len(flat), bool)
+    lib = rtx_lib()
+    cu, cv, cf = C.c_double(), C.c_double(), C.c_int()
+    fptr = C.POINTER(C.c_float)
+    for i in range(len(flat)):
+        _check(lib.rtx_frame_project(C.byref(frame), flat[i].ctypes.data_as(fptr), C.byref(cu), C.byref(cv), C.byref(cf)))
+        u[i], v[i], front[i] = cu.value, cv.value, bool(cf.value)
+    return u.reshape(pts.shape[:-1]), v.reshape(pts.shape[:-1]), front.reshape(pts.shape[:-1])
 
 
 def filter_params(**params):

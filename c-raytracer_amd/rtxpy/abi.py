@@ -279,6 +279,27 @@ class UpsampleStats(C.Structure):
 UPSAMPLE_DEFAULTS = {"scale": 2, "match_material": 1, "demodulate": 0, "sigma_normal": 0.05, "sigma_albedo": 0.1,
                      "sigma_plane": 0.02, "albedo_min": 1.0 / 64.0, "refine_threshold": 0.5}
 
+# temporal accumulation (rtx_frame_project, rtx_temporal*, rtx_render_temporal*)
+RTX_TEMPORAL_HISTORY_MAX = 65536
+RTX_TEMPORAL_E_MAX = 32.0
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("match_material", C.c_int32), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_plane", C.c_float), ("pad_", C.c_uint32)]
+
+
+class TemporalStats(C.Structure):
+    _fields_ = [("frames", C.c_uint32), ("pad_", C.c_uint32), ("render_ms", C.c_double), ("features_ms", C.c_double),
+                ("temporal_ms", C.c_double), ("pixels", C.c_uint64), ("live_pixels", C.c_uint64),
+                ("history_pixels", C.c_uint64), ("reset_pixels", C.c_uint64), ("closest_rays", C.c_uint64),
+                ("shadow_rays", C.c_uint64)]
+
+
+# rtx_temporal_params_default
+TEMPORAL_DEFAULTS = {"max_history": 32, "match_material": 1, "sigma_normal": 0.05, "sigma_albedo": 0.1,
+                     "sigma_plane": 0.02, "pad_": 0}
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -318,7 +339,9 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_pass_pack_host", "rtx_pass_unpack_host", "rtx_pass_pack_device", "rtx_pass_unpack_device",
                "rtx_upsample_params_default", "rtx_frame_scaled", "rtx_upsample", "rtx_upsample_device",
                "rtx_upsample_tiles", "rtx_upsample_tiles_device", "rtx_render_upsampled", "rtx_render_upsampled_device",
-               "rtx_get_upsample_stats"]
+               "rtx_get_upsample_stats",
+               "rtx_temporal_params_default", "rtx_frame_project", "rtx_temporal", "rtx_temporal_device",
+               "rtx_render_temporal", "rtx_render_temporal_device", "rtx_temporal_reset", "rtx_get_temporal_stats"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -582,6 +605,25 @@ def declare_rtx(lib):
     lib.rtx_render_upsampled_device.restype = C.c_int
     lib.rtx_get_upsample_stats.argtypes = [C.c_void_p, C.POINTER(UpsampleStats)]
     lib.rtx_get_upsample_stats.restype = C.c_int
+    lib.rtx_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]
+    lib.rtx_temporal_params_default.restype = None
+    lib.rtx_frame_project.argtypes = [C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int)]
+    lib.rtx_frame_project.restype = C.c_int
+    lib.rtx_temporal.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(Frame), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(Frame)] + [C.c_void_p] * 8
+    lib.rtx_temporal.restype = C.c_int
+    lib.rtx_temporal_device.argtypes = lib.rtx_temporal.argtypes + [C.c_void_p]
+    lib.rtx_temporal_device.restype = C.c_int
+    lib.rtx_render_temporal.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Params), C.POINTER(PassParams),
+                                        C.POINTER(TemporalParams)] + [C.c_void_p] * 4
+    lib.rtx_render_temporal.restype = C.c_int
+    lib.rtx_render_temporal_device.argtypes = lib.rtx_render_temporal.argtypes + [C.c_void_p]
+    lib.rtx_render_temporal_device.restype = C.c_int
+    lib.rtx_temporal_reset.argtypes = [C.c_void_p]
+    lib.rtx_temporal_reset.restype = C.c_int
+    lib.rtx_get_temporal_stats.argtypes = [C.c_void_p, C.POINTER(TemporalStats)]
+    lib.rtx_get_temporal_stats.restype = C.c_int
 
 
 def declare_oracle(lib):

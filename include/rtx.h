@@ -1077,6 +1077,117 @@ typedef struct rtx_upsample_stats {   /* the last rtx_upsample*, rtx_upsample_ti
 int rtx_get_upsample_stats(const rtx_ctx *ctx, rtx_upsample_stats *out);
 
 /*
+ * Temporal accumulation: the samples of the frames before carried into the current frame along a
+ * camera path, by reprojecting every pixel's world position into the previous frame.  The scene is static between
+ * uploads; only the camera moves.
+ *
+ * The projection.  Pixel (x, y) of a frame looks through corner + y step_y + (x + 1) step_x (render.c:353-363; the
+ * + 1 is the reference's).  rtx_frame_project (host only, no device needed), everything in double from the float
+ * fields: A = [step_x | step_y | corner - origin] (columns), M = A^-1 (adjugate over determinant), q = M (P - origin),
+ *     in_front = q2 > 0,   u = q0 / q2 - 1,   v = q1 / q2
+ * so a point seen by pixel (x, y) maps to (u, v) = (x, y).  RTX_ERR_ARG: a null argument, an empty frame, a
+ * determinant that is 0 or not finite, a non-finite entry of M; a refused call writes nothing.  The entries below
+ * form M once per call, on the host.
+ *
+ * The accumulation.  w and h are cur_frame's; c the current colour, Vc its variance of the mean, f its records; hc,
+ * Vh, L (a float per pixel: the number of frames a pixel's history holds) and g the colour, variance, length and
+ * records of the previous frame.  Pixel i = (x, y) is live iff f_i.z != 0 and c_i is finite (and, with variance,
+ * every component of Vc_i is finite and >= 0).  A pixel that is not live keeps the bits of c_i and Vc_i and gets
+ * length 0, and conf 1 where f_i.z == 0 (a miss has nothing to lose) and 0 otherwise.  For a live pixel (u, v) is
+ * P_i = f_i.position projected into prev_frame; IF THE TWO rtx_frame STRUCTS ARE BYTEWISE EQUAL, (u, v) = (x, y) BY
+ * DEFINITION (a hit point formed in float projects back up to 2e-3 pixels off its own pixel at 1920x1080, so a static
+ * camera would not be the identity numerically).  There is no history unless the point is in front, u and v are
+ * finite, -1 < u < w and -1 < v < h.  Otherwise x0 = floor(u), fx = (float)(u - x0), likewise y0 and fy, and the
+ * taps are j = (x0 + a, y0 + b), a, b in {0, 1}, of weight b_j = (a ? fx : 1 - fx) (b ? fy : 1 - fy) in float, in
+ * row-major order.  A tap is considered iff it lies inside the frame and b_j > 0, and accepted iff L_j >= 1 and
+ * finite, hc_j finite (and Vh_j finite and >= 0), g_j.z != 0, the materials equal (when match_material) and
+ * e <= RTX_TEMPORAL_E_MAX (a NaN is not), with
+ *     e   = |n_i-n_j|^2 / sigma_normal^2 + |a_i-a_j|^2 / sigma_albedo^2 + (n_i . (P_j-P_i))^2 / (sigma_plane z_i)^2
+ *     w_j = b_j exp(-e),   S = sum w_j,   conf = S          (the four b sum to 1, so S <= 1)
+ *     S > 0:  h = sum w_j hc_j / S,   H = sum w_j^2 Vh_j / S^2,   n = sum w_j L_j
+ *             n' = min(n, max_history - 1),   alpha = 1 / (n' + 1)
+ *             out = h + alpha (c_i - h),   V = (1 - alpha)^2 H + alpha^2 Vc_i,   len = n' + 1
+ *     S = 0:  out = c_i's bits,   V = Vc_i's bits,   len = 1,   conf = 0
+ * n is NOT divided by S: weight lost to rejected taps shortens the history.  With a static camera and unchanged
+ * records this is the cumulative mean of the frames up to max_history of them and an exponential mean from then on,
+ * and V is the exact variance of that weighted mean for independent frames.  After a reprojection the taps are
+ * correlated (neighbours share history pixels), so V guides a filter (rtx_denoise_variance) and is no error bar: the
+ * caveat rtx_denoise_variance's own variance carries.  View-dependent shading (specular highlights, reflections,
+ * refractions) is carried along with the surface point and lags behind a moving camera; max_history bounds the lag.
+ * One pixel per lane, no floating-point atomics: two runs give the same bits.  Needs no uploaded scene.
+ */
+#define RTX_TEMPORAL_HISTORY_MAX 65536u
+#define RTX_TEMPORAL_E_MAX 32.f
+typedef struct rtx_temporal_params {
+	uint32_t max_history;     /* 1..RTX_TEMPORAL_HISTORY_MAX, default 32: the new frame's weight never falls below 1/max_history */
+	int32_t match_material;   /* default 1: a tap of another material is rejected */
+	float sigma_normal, sigma_albedo, sigma_plane;   /* each > 0; INFINITY switches its term off.  Defaults 0.05 / 0.1 /
+	                           * 0.02 (rtx_denoise's) */
+	uint32_t pad_;
+} rtx_temporal_params;
+void rtx_temporal_params_default(rtx_temporal_params *p);
+int rtx_frame_project(const rtx_frame *frame, const float P[3], double *u, double *v, int *in_front);
+/* HOST buffers of cur_frame's w x h pixels: rgb, variance, hist_rgb, hist_variance, out_rgb and out_variance 3 floats per
+ * pixel, hist_length, out_length and out_conf one, features and hist_features one record.  variance, out_variance and
+ * (where there is a history) hist_variance are all given or all NULL.  prev_frame, hist_rgb, hist_length and
+ * hist_features are all given or all NULL (then hist_variance is NULL too); all NULL means the first frame: every live
+ * pixel takes the S = 0 branch.  out_conf may be NULL.  The outputs may alias the current inputs (out_rgb == rgb,
+ * out_variance == variance): a pixel's outputs depend on the current frame through that pixel alone.  They may not
+ * overlap the history.
+ * RTX_ERR_ARG before anything is launched: a null context, params, cur_frame, rgb, features, out_rgb or out_length,
+ * the pointer rules above, an output that overlaps a history buffer, max_history outside
+ * 1..RTX_TEMPORAL_HISTORY_MAX, a sigma that is <= 0 or NaN, w * h == 0 or above RTX_RAYS_MAX, a prev_frame of another
+ * size, and what rtx_frame_project refuses about prev_frame. */
+int rtx_temporal(rtx_ctx *ctx, const rtx_temporal_params *params, const rtx_frame *cur_frame, const float *rgb,
+		 const float *variance, const rtx_feature *features, const rtx_frame *prev_frame, const float *hist_rgb,
+		 const float *hist_variance, const float *hist_length, const rtx_feature *hist_features, float *out_rgb,
+		 float *out_variance, float *out_length, float *out_conf);
+/* Same on DEVICE buffers (both feature buffers 16-byte aligned, RTX_ERR_ARG otherwise; the others 4-byte aligned),
+ * enqueued on `stream` (NULL = the context's own); synchronises it. */
+int rtx_temporal_device(rtx_ctx *ctx, const rtx_temporal_params *params, const rtx_frame *cur_frame, const void *d_rgb,
+			const void *d_variance, const void *d_features, const rtx_frame *prev_frame, const void *d_hist_rgb,
+			const void *d_hist_variance, const void *d_hist_length, const void *d_hist_features, void *d_out_rgb,
+			void *d_out_variance, void *d_out_length, void *d_out_conf, void *stream);
+/*
+ * The pipeline along a camera path: rtx_render_passes_device of the frame; rtx_frame_features_device with
+ * params->u32conv; rtx_temporal_device against the history the context holds, which is the previous call's rgb,
+ * variance, length, records and rtx_frame (two sets of device buffers used in turn, 76 bytes per pixel each); the
+ * results become the history.  There is no history on the first call, after rtx_temporal_reset, after
+ * rtx_upload_scene, and when the frame's size differs from the history's.  rgb, variance and length are bit for bit
+ * what the three public calls chained by hand give, z is the render's.
+ * THE CALLER VARIES params->seed FROM FRAME TO FRAME (by at least pp->passes, as pass k renders with seed + k): with
+ * the same seed successive frames are correlated and the variance is wrong.
+ * HOST buffers rgb[W*H*3], z[W*H], variance[W*H*3], length[W*H]; each may be NULL.
+ * Errors as rtx_render_passes (RTX_ERR_STATE before an upload) and what rtx_temporal refuses about tp, all raised
+ * before anything is launched; a failed call leaves the history as it was.  rtx_get_stats and rtx_get_pass_stats
+ * afterwards describe the call's render as they would after rtx_render_passes, rtx_get_denoise_stats its feature call.
+ * Not covered: device groups, the filtered and the adaptive renders as the first step (chain rtx_temporal after them),
+ * objects that move.
+ */
+int rtx_render_temporal(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			const rtx_temporal_params *tp, float *rgb, float *z, float *variance, float *length);
+/* Same into DEVICE buffers (16-byte aligned, each may be NULL), enqueued on `stream` (NULL = the context's own);
+ * synchronises the stream. */
+int rtx_render_temporal_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_params *params, const rtx_pass_params *pp,
+			       const rtx_temporal_params *tp, void *d_rgb, void *d_z, void *d_variance, void *d_length,
+			       void *stream);
+/* Forgets the context's history (its buffers stay allocated): the next rtx_render_temporal* is a first frame. */
+int rtx_temporal_reset(rtx_ctx *ctx);
+typedef struct rtx_temporal_stats {   /* the last rtx_temporal* or rtx_render_temporal* of the context */
+	uint32_t frames, pad_;           /* rtx_render_temporal*: calls since the history was last forgotten, this one included;
+	                                  * rtx_temporal*: 0 */
+	double render_ms;                /* rtx_render_temporal*: rtx_pass_stats' render_ms + accum_ms of the call's render */
+	double features_ms;              /* ... its feature call, HIP events */
+	double temporal_ms;              /* the accumulation kernel, HIP events */
+	uint64_t pixels;                 /* w * h */
+	uint64_t live_pixels;            /* ... of which live */
+	uint64_t history_pixels;         /* live pixels with S > 0 */
+	uint64_t reset_pixels;           /* live pixels with S == 0: live_pixels = history_pixels + reset_pixels */
+	uint64_t closest_rays, shadow_rays;   /* rtx_render_temporal*: the call's render */
+} rtx_temporal_stats;
+int rtx_get_temporal_stats(const rtx_ctx *ctx, rtx_temporal_stats *out);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
