@@ -105,7 +105,7 @@ extern "C" int rtx_open(int device, rtx_ctx **out)
 	 * ~30 ms inside the first BVH build), and the runtime's pageable-copy path primed */
 	for (hipError_t (*load)(void) : { rtx_load_build, rtx_load_wide8_dev, rtx_load_shadow, rtx_load_trace, rtx_load_sort,
 					  rtx_load_post, rtx_load_gather, rtx_load_denoise, rtx_load_denoise_variance, rtx_load_passes,
-					  rtx_load_adaptive, rtx_load_filter, rtx_load_upsample, rtx_load_temporal })
+					  rtx_load_adaptive, rtx_load_filter, rtx_load_upsample, rtx_load_temporal, rtx_load_projection })
 		if ((e = load()) != hipSuccess) {
 			rtx_close(c);
 			return fail(RTX_ERR_HIP, "loading the device code failed: %s", hipGetErrorString(e));

@@ -72,26 +72,30 @@ static int features_check(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, cons
 	return RTX_OK;
 }
 
-/* checked arguments, d_features on the device: the frame's rays, their closest hits, the records (the upsampling
- * pipeline's two feature calls too, rtx_upsample.cpp) */
-int rtx_features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, hipStream_t stream)
+/* checked arguments, d_features on the device: n rays (the frame's own, formed here, or with d_rays a caller's), their
+ * closest hits, the records */
+static int features_body(rtx_ctx *c, const rtx_frame *fr, uint32_t n, const float4 *d_rays, int32_t u32conv, void *d_features,
+			 hipStream_t stream)
 {
 	if ((uintptr_t)d_features & 15u)
 		return fail(RTX_ERR_ARG, "feature buffer must be 16-byte aligned");
-	const uint32_t n = fr->width * fr->height;
-	if (c->d_dn_rays.grow((size_t)n * sizeof(rtx_ray)) != hipSuccess || c->d_dn_hits.grow((size_t)n * sizeof(rtx_hit)) != hipSuccess)
+	if ((!d_rays && c->d_dn_rays.grow((size_t)n * sizeof(rtx_ray)) != hipSuccess) ||
+	    c->d_dn_hits.grow((size_t)n * sizeof(rtx_hit)) != hipSuccess)
 		return fail(RTX_ERR_NOMEM, "rays and hits of %u pixels", n);
-	const DFrame F = rtx_dframe(fr);
 	HIP_TRY(hipEventRecord(c->ev0, stream));
-	HIP_TRY(rtx_launch_frame_rays(&F, c->d_dn_rays, stream));
+	if (!d_rays) {
+		const DFrame F = rtx_dframe(fr);
+		HIP_TRY(rtx_launch_frame_rays(&F, c->d_dn_rays, stream));
+		d_rays = c->d_dn_rays;
+	}
 	/* the query is the ray queries' own; the caller's rtx_get_ray_stats stays that of their last query */
 	const rtx_ray_stats saved = c->ray_stats;
-	const int rc = rtx_rays_common(c, n, c->d_dn_rays, c->d_dn_hits, 0, stream);
+	const int rc = rtx_rays_common(c, n, d_rays, c->d_dn_hits, 0, stream);
 	const uint64_t hits = c->ray_stats.hits;
 	c->ray_stats = saved;
 	if (rc)
 		return rc;
-	HIP_TRY(rtx_launch_dn_features(n, c->d_dn_rays, c->d_dn_hits, c->scene.mats, u32conv,
+	HIP_TRY(rtx_launch_dn_features(n, d_rays, c->d_dn_hits, c->scene.mats, u32conv,
 				       (float4 *)d_features, stream));
 	HIP_TRY(hipEventRecord(c->ev1, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
@@ -101,6 +105,19 @@ int rtx_features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *
 	c->dn_stats.pixels = n;
 	c->dn_stats.hit_pixels = hits;
 	return RTX_OK;
+}
+
+/* the frame's own rays (the upsampling pipeline's two feature calls too, rtx_upsample.cpp) */
+int rtx_features_common(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, hipStream_t stream)
+{
+	return features_body(c, fr, fr->width * fr->height, nullptr, u32conv, d_features, stream);
+}
+
+/* a caller's rays (rtx_ray_features*, rtx_rays_render.cpp) */
+int rtx_ray_features_common(rtx_ctx *c, uint32_t w, uint32_t h, const void *d_rays, int32_t u32conv, void *d_features,
+			    hipStream_t stream)
+{
+	return features_body(c, nullptr, w * h, (const float4 *)d_rays, u32conv, d_features, stream);
 }
 
 extern "C" int rtx_frame_features_device(rtx_ctx *c, const rtx_frame *fr, int32_t u32conv, void *d_features, void *stream)

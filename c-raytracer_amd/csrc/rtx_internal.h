@@ -216,6 +216,8 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float4> d_dn_feat;            /* the host-buffer calls' device copies */
 	DevBuf<float> d_dn_rgb, d_dn_var;
 	DevBuf<unsigned long long> d_dn_ctr; /* k_dn_pack's hit-pixel count */
+	/* ray batches (rtx_render_rays*, rtx_ray_features, rtx_render_projection*): grow-only scratch of its own */
+	DevBuf<float4> d_rr_rays;            /* the host-buffer calls' device copy of the rays; a projection's generated rays */
 	rtx_denoise_stats dn_stats{};
 	/* multi-pass rendering (rtx_render_passes*): grow-only scratch of its own */
 	DevBuf<float> d_pass_rgb;     /* the pass being rendered */
@@ -360,9 +362,15 @@ uint32_t rtx_wide8_build(const std::vector<DNode> &inner, uint32_t nnodes, const
 			 const float lo[3], const float hi[3], const std::vector<uint32_t> &skip_objs, const DTreeFrame &tf,
 			 double fpad, QFrame &F, bool &skipped, std::vector<DW8> &out, std::vector<uint32_t> &leafmap);
 /* one frame (or tile shard) into device buffers on stream.  d_tiles: a checked device list of n_tiles tile indices
- * (strictly increasing, below the frame's tile count) to render instead, with tile sharding 0/1 */
+ * (strictly increasing, below the frame's tile count) to render instead, with tile sharding 0/1.  d_prim_rays: the
+ * fr->width * fr->height rtx_ray records of a ray batch (16-byte aligned, no tile list) in place of the frame's own
+ * primary rays; fr then gives the size alone, and the shade-points-per-tile estimate is neither read nor written */
 int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z, hipStream_t stream,
-		      const uint32_t *d_tiles = nullptr, uint32_t n_tiles = 0);
+		      const uint32_t *d_tiles = nullptr, uint32_t n_tiles = 0, const void *d_prim_rays = nullptr);
+/* rtx_rays_render.cpp: checked arguments, both buffers on the device (16-byte aligned): the closest hits of the w * h
+ * rays d_rays as feature records, on stream (synchronised); fills c->dn_stats */
+RTX_HIDDEN int rtx_ray_features_common(rtx_ctx *c, uint32_t w, uint32_t h, const void *d_rays, int32_t u32conv, void *d_features,
+				       hipStream_t stream);
 /* rtx_scene.cpp: c's scene buffers freed (c's device current) */
 RTX_HIDDEN void rtx_free_scene(rtx_ctx *c);
 /* rtx_query.cpp: n checked rays on device buffers into c->ray_stats (the feature buffers' query too) */

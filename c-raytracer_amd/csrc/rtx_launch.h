@@ -53,14 +53,18 @@ RTX_HIDDEN hipError_t rtx_load_wide8_dev(void);
 /* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays.  tile_list: the device list of a tile-list render
  * (rtx_render_tiles*), indexed by the chunk positions tile_begin..; null: the shard of P.  pack: the packed GI
  * walk's region (RTX_OPT_TRACE_PACK), waves * rtx_trace_pack_bytes(pack_seg) bytes, for a scene that walks the
- * 8-wide tree (S->trace_w8); null: every GI batch walks on its own */
+ * 8-wide tree (S->trace_w8); null: every GI batch walks on its own.  prim_rays: the F->width * F->height rtx_ray
+ * records of a ray batch (rtx_render_rays*), 16-byte aligned, in place of the frame's own primary rays (no
+ * tile_list then); null: the pinhole frame F.  Every instance is capped to the occupancy rtx_trace_occupancy
+ * reports for the default one (__launch_bounds__), so one query sizes every launch. */
 size_t rtx_trace_pack_bytes(uint32_t pack_seg);
 size_t rtx_trace_lds_bytes(uint32_t stack_size);
 hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu);
 hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const DParams *P, float *rgb, float *z, DTask *tasks,
 			    uint32_t task_cap, float4 *staging, uint32_t staging_cap, float4 *sp_out, uint32_t sp_cap,
 			    uint2 *tile_rec, uint32_t tile_begin, uint32_t tile_end, unsigned long long *ctr, uint32_t waves,
-			    int count, const uint32_t *tile_list, void *pack, uint32_t pack_seg, hipStream_t stream);
+			    int count, const uint32_t *tile_list, void *pack, uint32_t pack_seg, const float4 *prim_rays,
+			    hipStream_t stream);
 hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec, const float4 *contrib,
 			    uint32_t tile_begin, uint32_t ntiles, float *rgb, const uint32_t *tile_list, hipStream_t stream);
 size_t rtx_rays_lds_bytes(uint32_t stack_size);
@@ -184,6 +188,11 @@ RTX_HIDDEN hipError_t rtx_launch_temporal(uint32_t w, uint32_t h, const rtx_temp
 					  float *out_rgb, float *out_var, float *out_len, float *out_conf, unsigned long long *ctr,
 					  hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_temporal(void);
+
+/* rtx_projection.hip: the rays of a panoramic, fisheye or orthographic camera (rtx_projection.h) */
+struct rtx_proj_basis;
+RTX_HIDDEN hipError_t rtx_launch_projection_rays(const rtx_proj_basis *B, float4 *rays, hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_projection(void);
 
 }
 

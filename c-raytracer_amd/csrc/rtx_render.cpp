@@ -1,6 +1,7 @@
 /*
  * C-ABI of include/rtx.h, the render (replaces render_init + render, render.c:61-116 / 345-368):
- * a frame, a tile shard or a caller's list of tiles (rtx_render_tiles*) in chunks of tiles through k_trace,
+ * a frame, a tile shard, a caller's list of tiles (rtx_render_tiles*) or a caller's primary rays (rtx_render_rays*,
+ * rtx_rays_render.cpp) in chunks of tiles through k_trace,
  * the shade-point sort, k_shadow and k_accum, and its statistics.
  */
 #include <hip/hip_runtime.h>
@@ -15,7 +16,7 @@
 #include "rtx_tiles.h"
 
 int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, float *d_rgb, float *d_z,
-			 hipStream_t stream, const uint32_t *d_tiles, uint32_t n_tiles)
+			 hipStream_t stream, const uint32_t *d_tiles, uint32_t n_tiles, const void *d_prim_rays)
 {
 	if (!c->have_scene)
 		return fail(RTX_ERR_STATE, "rtx_render before rtx_upload_scene");
@@ -82,7 +83,8 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	memcpy(&sp_key.v[15], F.step_y, 12);
 	memcpy(&sp_key.v[18], F.origin, 12);
 	sp_key.set = 1;
-	if (c->sp_tile_key == sp_key && c->sp_tile_seen > 0.0)
+	/* a ray batch (rtx_render_rays*) has no camera to key the estimate with: it neither reads nor writes it */
+	if (!d_prim_rays && c->sp_tile_key == sp_key && c->sp_tile_seen > 0.0)
 		avg_tile = std::min<uint64_t>(avg_tile, (uint64_t)(c->sp_tile_seen * 1.25) + 64);
 	if (c->opt_sp_tile) /* RTX_OPT_SP_PER_TILE: tests drive the overflow path with a low figure */
 		avg_tile = c->opt_sp_tile;
@@ -149,7 +151,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 		HIP_TRY(rtx_launch_trace(&c->scene, &F, &P, d_rgb, d_z, c->d_tasks, task_cap, c->d_staging,
 					 (uint32_t)staging_cap, c->d_sp, sp_cap, c->d_tile_rec, begin, end, c->d_ctr,
 					 std::min<uint32_t>(waves, end - begin), p->count_traversal, d_tiles,
-					 pack ? (void *)c->d_pack : nullptr, pack_seg, stream));
+					 pack ? (void *)c->d_pack : nullptr, pack_seg, (const float4 *)d_prim_rays, stream));
 		HIP_TRY(hipEventRecord(c->ev[1], stream));
 		unsigned long long head[RTX_C_N];
 		HIP_TRY(hipMemcpyAsync(head, c->d_ctr, sizeof(head), hipMemcpyDeviceToHost, stream));
@@ -251,7 +253,7 @@ int rtx_render_common(rtx_ctx *c, const rtx_frame *fr, const rtx_params *p, floa
 	HIP_TRY(hipEventRecord(c->ev1, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
 	/* a list render reads the estimate (the whole frame's settings key it) and leaves it as it is */
-	if (P.ntiles && !d_tiles) {
+	if (P.ntiles && !d_tiles && !d_prim_rays) {
 		c->sp_tile_seen = (double)shade_points / P.ntiles;
 		c->sp_tile_key = sp_key;
 	}

@@ -811,17 +811,31 @@ template <> struct TileList<true> {
 	const uint32_t *__restrict__ p;
 };
 
-template <bool COUNT, bool LIST, bool PACK>
+/* Where a pixel's primary ray comes from: RAYS = false, the pinhole frame (RTX_PRIMARY_DIR), and no argument;
+ * RAYS = true, a caller's width * height rtx_ray records, row-major (rtx_render_rays*): pixel (px, py) loads
+ * record py * width + px, two float4 per lane, and takes its origin and dir.  A record whose tmax is 0,
+ * negative or -INFINITY is a hole: the lane is idle from the start, its pixel rgb 0 and z 0, no ray traced or
+ * counted; every other tmax (a finite positive one and NaN too) is an unbounded primary ray.  The pointer is
+ * a kernel argument of the true instances alone and not a field of DParams, like TileList's.  (The record
+ * follows sp_cap, where the empty one lies in the argument block's padding: after `pack` it moved the
+ * packed instances' hidden arguments by 8 bytes.) */
+template <bool RAYS> struct PrimaryRays {};
+template <> struct PrimaryRays<true> {
+	const float4 *__restrict__ p;
+};
+
+template <bool COUNT, bool LIST, bool PACK, bool RAYS = false>
 #ifndef RTX_TRACE_OCC
 #define RTX_TRACE_OCC 6 /* waves per SIMD k_trace is register-capped for (80 VGPRs; with 9 LDS stack entries, 24 waves per CU) */
 #endif
 __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame F, DParams P, float *__restrict__ rgb,
 						float *__restrict__ zbuf, DTask *__restrict__ tasks, uint32_t task_cap,
 						float4 *__restrict__ staging, uint32_t staging_cap,
-						float4 *__restrict__ sp_out, uint32_t sp_cap, uint2 *__restrict__ tile_rec,
-						uint32_t tile_begin, uint32_t tile_end, unsigned long long *__restrict__ ctr,
-						TileList<LIST> tile_list, TracePack<PACK> pack)
+						float4 *__restrict__ sp_out, uint32_t sp_cap, PrimaryRays<RAYS> prays,
+						uint2 *__restrict__ tile_rec, uint32_t tile_begin, uint32_t tile_end,
+						unsigned long long *__restrict__ ctr, TileList<LIST> tile_list, TracePack<PACK> pack)
 {
+	static_assert(!(RAYS && LIST), "tile lists of ray batches are not built");
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	float *gp_tab = (float *)lds_raw;
 	uint32_t *off = (uint32_t *)(lds_raw + WAVE * SPW * 4);
@@ -865,7 +879,16 @@ __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame 
 		uint32_t rb = P.max_bounces, inside = RTX_NONE, slot = lane_id();
 		uint64_t key = 0;
 		bool primary = true;
-		if (act) {
+		if constexpr (RAYS) {
+			if (act) {
+				const size_t rec = (size_t)py * F.width + px;
+				const float4 r0 = prays.p[2 * rec], r1 = prays.p[2 * rec + 1];
+				o = mk3(r0.x, r0.y, r0.z);
+				d = mk3(r1.x, r1.y, r1.z);
+				act = !(r0.w <= 0.f); /* a hole; NaN stays a ray */
+				key = rtx_key_pixel(P.seed, py * F.width + px);
+			}
+		} else if (act) {
 			RTX_PRIMARY_DIR(F, px, py, o, d);
 			key = rtx_key_pixel(P.seed, py * F.width + px);
 		}
@@ -1362,21 +1385,43 @@ extern "C" hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const D
 				       DTask *tasks, uint32_t task_cap, float4 *staging, uint32_t staging_cap,
 				       float4 *sp_out, uint32_t sp_cap, uint2 *tile_rec, uint32_t tile_begin,
 				       uint32_t tile_end, unsigned long long *ctr, uint32_t waves, int count,
-				       const uint32_t *tile_list, void *pack, uint32_t pack_seg, hipStream_t stream)
+				       const uint32_t *tile_list, void *pack, uint32_t pack_seg, const float4 *prim_rays,
+				       hipStream_t stream)
 {
 	const size_t lds = rtx_trace_lds_bytes(S->stack_size);
 	if (pack && (!S->trace_w8 || !pack_seg || pack_seg % WAVE)) /* the packed instances walk the 8-wide tree alone */
 		return hipErrorInvalidValue;
+	if (prim_rays) { /* a ray batch (rtx_render_rays*): the whole image or a shard, never a tile list */
+		if (tile_list)
+			return hipErrorInvalidValue;
+#define RTX_TRACE_LAUNCH_RAYS(C, K)                                                                                            \
+	hipLaunchKernelGGL((k_trace<C, false, K, true>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,       \
+			   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<true>{ prim_rays }, tile_rec, tile_begin,   \
+			   tile_end, ctr, TileList<false>{}, pk##K)
+		const TracePack<true> pktrue{ (unsigned char *)pack, pack_seg };
+		const TracePack<false> pkfalse{};
+		if (pack && count)
+			RTX_TRACE_LAUNCH_RAYS(true, true);
+		else if (pack)
+			RTX_TRACE_LAUNCH_RAYS(false, true);
+		else if (count)
+			RTX_TRACE_LAUNCH_RAYS(true, false);
+		else
+			RTX_TRACE_LAUNCH_RAYS(false, false);
+#undef RTX_TRACE_LAUNCH_RAYS
+		return hipGetLastError();
+	}
 #define RTX_TRACE_LAUNCH(C, L, ...)                                                                                            \
 	do {                                                                                                                    \
 		if (pack)                                                                                                       \
 			hipLaunchKernelGGL((k_trace<C, L, true>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,  \
-					   task_cap, staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr,     \
-					   TileList<L>{ __VA_ARGS__ }, TracePack<true>{ (unsigned char *)pack, pack_seg });        \
+					   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<false>{}, tile_rec,          \
+					   tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ },                                  \
+					   TracePack<true>{ (unsigned char *)pack, pack_seg });                                    \
 		else                                                                                                            \
 			hipLaunchKernelGGL((k_trace<C, L, false>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, \
-					   task_cap, staging, staging_cap, sp_out, sp_cap, tile_rec, tile_begin, tile_end, ctr,     \
-					   TileList<L>{ __VA_ARGS__ }, TracePack<false>{});                                        \
+					   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<false>{}, tile_rec,          \
+					   tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ }, TracePack<false>{});             \
 	} while (0)
 	if (tile_list && count)
 		RTX_TRACE_LAUNCH(true, true, tile_list);

@@ -36,7 +36,13 @@
  *                guidance of the full-resolution feature records, and the 8x8 tiles that hold a pixel of confidence
  *                below T (default 0.5) re-rendered at full resolution (rtx_render_upsampled).  One GPU; implies
  *                nothing else, composes with --denoise, not with the multi-pass flags
+ *   --projection panorama | fisheye DEGREES | ortho EXTENT   another camera model that looks where the scene's camera
+ *                looks (rtx_render_projection): an equirectangular panorama of the full 360 degrees across the width, an
+ *                equidistant fisheye of that full angle across the width, or an orthographic view EXTENT scene units wide
+ *                (0: the image plane's own width).  One GPU; composes with --denoise (rtx_ray_features of the
+ *                rtx_projection_ray rays), not with the multi-pass flags or --upsample
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -77,7 +83,8 @@ static const char *HELPTEXT =
 	"[--filter-radius] (float)        : DEFAULT = 1.5     : with --filter: the filter's radius in pixels (box 0.5..2.5, the others 1..2.5).\n"
 	"[--filter-alpha] (float)         : DEFAULT = 2       : with --filter gaussian: the falloff exp(-alpha d^2).\n"
 	"[--upsample] (integer)           : DEFAULT = OFF     : render at 1/S of the resolution per axis (S in 1..8), upsample guided by the full-resolution features, refine the uncertain tiles (one GPU only, not with the multi-pass flags).\n"
-	"[--refine] (float)               : DEFAULT = 0.5     : with --upsample: re-render at full resolution the 8x8 tiles that hold a pixel of confidence below this.\n";
+	"[--refine] (float)               : DEFAULT = 0.5     : with --upsample: re-render at full resolution the 8x8 tiles that hold a pixel of confidence below this.\n"
+	"[--projection] (panorama | fisheye DEGREES | ortho EXTENT) : DEFAULT = OFF : a 360 degree panorama, an equidistant fisheye of that angle across the width, or an orthographic view that wide, looking where the camera looks (one GPU only, not with the multi-pass flags or --upsample).\n";
 
 static struct timespec t0;
 static int log_cpu = 0;
@@ -253,6 +260,50 @@ int main(int argc, char **argv)
 		LOG("--refine needs --upsample.");
 		return 1;
 	}
+	/* a camera model other than the pinhole (rtx_render_projection): the scene's camera gives the view direction */
+	rtx_projection proj;
+	rtx_projection_default(&proj);
+	int projection = 0;
+	for (int i = 1; i < argc; i++)
+		if (!strcmp(argv[i], "--projection"))
+			projection = i;
+	if (projection) {
+		const char *name = projection + 1 < argc ? argv[projection + 1] : "";
+		const char *arg = projection + 2 < argc ? argv[projection + 2] : NULL;
+		if (!strcmp(name, "panorama")) {
+			proj.kind = RTX_PROJ_PANORAMA;
+		} else if (!strcmp(name, "fisheye") && arg) {
+			proj.kind = RTX_PROJ_FISHEYE;
+			proj.fov = (float)(atof(arg) * (3.14159265358979323846 / 180.0));
+			if (!(proj.fov > 0.f) || atof(arg) > 360.0) {
+				LOG("--projection fisheye needs an angle in (0, 360] degrees, not '%s'.", arg);
+				return 1;
+			}
+		} else if (!strcmp(name, "ortho") && arg) {
+			proj.kind = RTX_PROJ_ORTHO;
+			proj.extent = (float)atof(arg);
+			if (!(proj.extent >= 0.f) || isinf(proj.extent)) {
+				LOG("--projection ortho needs a width of at least 0 (0: the image plane's own), not '%s'.", arg);
+				return 1;
+			}
+		} else {
+			LOG("--projection needs panorama, fisheye DEGREES or ortho EXTENT.");
+			return 1;
+		}
+		if (ngpu > 1) {
+			LOG("--projection renders on one GPU, not on %d.", ngpu);
+			return 1;
+		}
+		if (multipass || denoise_variance) {
+			LOG("--projection does not combine with --passes, --aa, --lens, --filter, --adaptive, --target-error or "
+			    "--denoise-variance: move rtx_projection's offsets and average the renders through the library instead.");
+			return 1;
+		}
+		if (upsample) {
+			LOG("--projection does not combine with --upsample: the upsampler's scaled frame is a pinhole's.");
+			return 1;
+		}
+	}
 
 	LOG("Loading scene.");
 	const char *scale = NULL;
@@ -336,6 +387,18 @@ int main(int argc, char **argv)
 		closest = us.closest_rays;
 		shadow = us.shadow_rays;
 		kms = us.low_ms + us.features_ms + us.upsample_ms + us.refine_ms;
+	} else if (projection) {
+		rtx_ctx *ctx = NULL;
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_render_projection(ctx, &fr, &proj, &p, rgb, z) ||
+		    rtx_get_stats(ctx, &st)) {
+			LOG("%s", rtx_last_error());
+			rtx_close(ctx);
+			return 1;
+		}
+		rtx_close(ctx);
+		closest = st.closest_rays;
+		shadow = st.shadow_rays;
+		kms = st.kernel_ms;
 	} else {
 		rtx_group *grp = NULL;
 		if (rtx_group_open(ngpu, devs, &grp) || rtx_group_upload_scene(grp, desc) ||
@@ -387,11 +450,19 @@ int main(int argc, char **argv)
 		rtx_denoise_params dp;
 		rtx_denoise_stats ds;
 		rtx_denoise_params_default(&dp);
-		if (!feat) {
+		/* a projection's records: rtx_ray_features of its rays, formed on the host by their definition */
+		rtx_ray *rays = projection ? malloc(px * sizeof(rtx_ray)) : NULL;
+		if (!feat || (projection && !rays)) {
 			LOG("Unable to allocate the feature buffer.");
 			return 1;
 		}
-		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) || rtx_frame_features(ctx, &fr, p.u32conv, feat) ||
+		for (size_t i = 0; rays && i < px; i++)
+			if (rtx_projection_ray(&fr, &proj, (uint32_t)(i % w), (uint32_t)(i / w), &rays[i])) {
+				LOG("%s", rtx_last_error());
+				return 1;
+			}
+		if (rtx_open(dev0, &ctx) || rtx_upload_scene(ctx, desc) ||
+		    (projection ? rtx_ray_features(ctx, w, h, rays, p.u32conv, feat) : rtx_frame_features(ctx, &fr, p.u32conv, feat)) ||
 		    rtx_denoise(ctx, w, h, &dp, feat, rgb) || rtx_get_denoise_stats(ctx, &ds)) {
 			LOG("%s", rtx_last_error());
 			rtx_close(ctx);
@@ -399,6 +470,7 @@ int main(int argc, char **argv)
 		}
 		rtx_close(ctx);
 		free(feat);
+		free(rays);
 		LOG("Denoised %llu hit pixels: features %.3f ms, %u filter levels %.3f ms.", (unsigned long long)ds.hit_pixels,
 		    ds.features_ms, ds.iterations, ds.filter_ms);
 	}

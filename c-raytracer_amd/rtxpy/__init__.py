@@ -714,6 +714,100 @@ class Renderer:
         _check(self.lib.rtx_get_temporal_stats(self._ctx, C.byref(s)))
         return s
 
+    @staticmethod
+    def _ray_batch(rays_or_origins, dirs, shape):
+        """a render_rays / ray_features batch as (records (h * w,) of abi.RAY_DTYPE, h, w, n): the records as given
+        with `shape`, else padded with holes to w = min(8 * ceil(n / 8), 1024), h = ceil(n / w)"""
+        if dirs is None:
+            rays = np.ascontiguousarray(rays_or_origins, dtype=abi.RAY_DTYPE)
+            if shape is None and rays.ndim == 2:
+                shape = rays.shape
+            rays = rays.reshape(-1)
+        else:
+            origins = np.asarray(rays_or_origins, np.float32).reshape(-1, 3)
+            d = np.asarray(dirs, np.float32).reshape(-1, 3)
+            if origins.shape != d.shape:
+                raise ValueError("origins and dirs differ in shape")
+            rays = np.zeros(len(origins), abi.RAY_DTYPE)
+            rays["origin"], rays["dir"], rays["tmax"] = origins, d, np.inf
+        n = len(rays)
+        if n == 0:
+            raise ValueError("an empty ray batch")
+        if shape is not None:
+            h, w = shape
+            if h * w != n:
+                raise ValueError(f"shape {shape} does not hold {n} rays")
+            return rays, h, w, n
+        w = min(8 * ((n + 7) // 8), 1024)
+        h = (n + w - 1) // w
+        padded = np.zeros(h * w, abi.RAY_DTYPE)  # a hole: tmax 0
+        padded[:n] = rays
+        return padded, h, w, n
+
+    def render_rays(self, rays_or_origins, dirs=None, params=None, shape=None):
+        """rtx_render_rays on host arrays: a frame whose primary rays are the caller's.  rays_or_origins: records of
+        abi.RAY_DTYPE (tmax <= 0: a hole), or origins (n, 3) with dirs (n, 3) (unbounded rays).  shape=(h, w): the
+        batch is that image, returns (rgb (h, w, 3), z (h, w)); a 2-D record array is its own shape.  Without a
+        shape the batch is padded with holes and (rgb (n, 3), z (n,)) of the first n pixels come back."""
+        rays, h, w, n = self._ray_batch(rays_or_origins, dirs, shape)
+        p = default_params() if params is None else params
+        rgb, z = np.zeros((h * w, 3), np.float32), np.zeros(h * w, np.float32)
+        _check(self.lib.rtx_render_rays(self._ctx, w, h, rays.ctypes.data, C.byref(p), rgb.ctypes.data, z.ctypes.data))
+        if shape is not None or (dirs is None and np.ndim(rays_or_origins) == 2):
+            return rgb.reshape(h, w, 3), z.reshape(h, w)
+        return rgb[:n].copy(), z[:n].copy()
+
+    def render_rays_device(self, width, height, d_rays, params, d_rgb, d_z, stream=None):
+        """rtx_render_rays_device: d_rays a device pointer (int, 16-byte aligned) to width * height rtx_ray records,
+        d_rgb / d_z device pointers or None; stream: hipStream_t as int or None."""
+        _check(self.lib.rtx_render_rays_device(self._ctx, width, height, C.c_void_p(d_rays), C.byref(params),
+                                               C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                               C.c_void_p(stream) if stream else None))
+
+    def ray_features(self, rays_or_origins, dirs=None, u32conv=abi.RTX_U32_SAT, shape=None):
+        """rtx_ray_features on host arrays: features() of a ray batch (as render_rays takes it), (h, w) records of
+        abi.FEATURE_DTYPE, or the first n of a padded batch"""
+        rays, h, w, n = self._ray_batch(rays_or_origins, dirs, shape)
+        out = np.zeros(h * w, abi.FEATURE_DTYPE)
+        _check(self.lib.rtx_ray_features(self._ctx, w, h, rays.ctypes.data, u32conv, out.ctypes.data))
+        if shape is not None or (dirs is None and np.ndim(rays_or_origins) == 2):
+            return out.reshape(h, w)
+        return out[:n].copy()
+
+    def ray_features_device(self, width, height, d_rays, d_features, u32conv=abi.RTX_U32_SAT, stream=None):
+        """rtx_ray_features_device: d_rays / d_features are device pointers (ints, 16-byte aligned)"""
+        _check(self.lib.rtx_ray_features_device(self._ctx, width, height, C.c_void_p(d_rays), u32conv, C.c_void_p(d_features),
+                                                C.c_void_p(stream) if stream else None))
+
+    def projection_rays_device(self, frame, proj, d_rays, stream=None):
+        """rtx_projection_rays_device: the projection's width * height rays into the device buffer d_rays"""
+        _check(self.lib.rtx_projection_rays_device(self._ctx, C.byref(frame), C.byref(proj), C.c_void_p(d_rays),
+                                                   C.c_void_p(stream) if stream else None))
+
+    def projection_rays(self, frame, proj):
+        """the projection's rays as the device forms them, an (h, w) array of abi.RAY_DTYPE (a torch tensor holds them
+        on the device; in a process that has not used torch yet, call torch.cuda.init() before the first
+        Renderer, as bench.py does: torch ships its own HIP runtime)"""
+        import torch
+        buf = torch.zeros((frame.height * frame.width, 8), dtype=torch.float32, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(self.device)
+        self.projection_rays_device(frame, proj, buf.data_ptr())
+        return buf.cpu().numpy().view(abi.RAY_DTYPE).reshape(frame.height, frame.width)
+
+    def render_projection(self, frame, proj, params):
+        """rtx_render_projection on host arrays: (rgb (h, w, 3), z (h, w)) of the frame through projection(...)"""
+        w, h = frame.width, frame.height
+        rgb, z = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        _check(self.lib.rtx_render_projection(self._ctx, C.byref(frame), C.byref(proj), C.byref(params), rgb.ctypes.data,
+                                              z.ctypes.data))
+        return rgb, z
+
+    def render_projection_device(self, frame, proj, params, d_rgb, d_z, stream=None):
+        """rtx_render_projection_device: d_rgb / d_z device pointers (ints) or None"""
+        _check(self.lib.rtx_render_projection_device(self._ctx, C.byref(frame), C.byref(proj), C.byref(params),
+                                                     C.c_void_p(d_rgb) if d_rgb else None, C.c_void_p(d_z) if d_z else None,
+                                                     C.c_void_p(stream) if stream else None))
+
     def close(self):
         if self._ctx:
             self.lib.rtx_close(self._ctx)
@@ -794,6 +888,27 @@ def frame_project(frame, points):
         _check(lib.rtx_frame_project(C.byref(frame), flat[i].ctypes.data_as(fptr), C.byref(cu), C.byref(cv), C.byref(cf)))
         u[i], v[i], front[i] = cu.value, cv.value, bool(cf.value)
     return u.reshape(pts.shape[:-1]), v.reshape(pts.shape[:-1]), front.reshape(pts.shape[:-1])
+
+
+def projection(kind=None, **fields):
+    """rtx_projection_default plus overrides (kind: an abi.RTX_PROJ_* or "panorama" / "fisheye" / "ortho"; fov in
+    radians, extent, offset_x, offset_y)"""
+    p = abi.Projection()
+    rtx_lib().rtx_projection_default(C.byref(p))
+    if kind is not None:
+        p.kind = abi.PROJ_KINDS[kind] if isinstance(kind, str) else kind
+    for k, v in fields.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def projection_ray(frame, proj, px, py):
+    """rtx_projection_ray (no device needed): pixel (px, py)'s ray, one record of abi.RAY_DTYPE (tmax 0: a hole)"""
+    out = np.zeros(1, abi.RAY_DTYPE)
+    _check(rtx_lib().rtx_projection_ray(C.byref(frame), C.byref(proj), px, py, out.ctypes.data))
+    return out[0]
 
 
 def filter_params(**params):

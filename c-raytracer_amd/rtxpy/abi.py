@@ -300,6 +300,19 @@ class TemporalStats(C.Structure):
 TEMPORAL_DEFAULTS = {"max_history": 32, "match_material": 1, "sigma_normal": 0.05, "sigma_albedo": 0.1,
                      "sigma_plane": 0.02, "pad_": 0}
 
+# renders of a caller's rays and the camera models (rtx_render_rays*, rtx_ray_features*, rtx_projection*)
+RTX_PROJ_PANORAMA, RTX_PROJ_FISHEYE, RTX_PROJ_ORTHO = 0, 1, 2
+PROJ_KINDS = {"panorama": RTX_PROJ_PANORAMA, "fisheye": RTX_PROJ_FISHEYE, "ortho": RTX_PROJ_ORTHO}
+
+
+class Projection(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("fov", C.c_float), ("extent", C.c_float), ("offset_x", C.c_float),
+                ("offset_y", C.c_float)]
+
+
+# rtx_projection_default (fov: 2 pi rounded to float)
+PROJECTION_DEFAULTS = {"kind": RTX_PROJ_PANORAMA, "fov": 6.2831854820251465, "extent": 0.0, "offset_x": 0.0, "offset_y": 0.0}
+
 # rtx_pass_params_default
 PASS_DEFAULTS = {"passes": 1, "flags": 0, "aperture": 0.0, "focus": 1.0, "target_error": 0.0, "min_passes": 2}
 
@@ -341,7 +354,10 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_upsample_tiles", "rtx_upsample_tiles_device", "rtx_render_upsampled", "rtx_render_upsampled_device",
                "rtx_get_upsample_stats",
                "rtx_temporal_params_default", "rtx_frame_project", "rtx_temporal", "rtx_temporal_device",
-               "rtx_render_temporal", "rtx_render_temporal_device", "rtx_temporal_reset", "rtx_get_temporal_stats"]
+               "rtx_render_temporal", "rtx_render_temporal_device", "rtx_temporal_reset", "rtx_get_temporal_stats",
+               "rtx_render_rays", "rtx_render_rays_device", "rtx_ray_features", "rtx_ray_features_device",
+               "rtx_projection_default", "rtx_projection_ray", "rtx_projection_rays_device", "rtx_render_projection",
+               "rtx_render_projection_device"]
 RTX_SCENE_SYMBOLS = ["rtx_scene_load", "rtx_scene_parse", "rtx_scene_desc_of", "rtx_scene_num_json_objects",
                      "rtx_scene_free", "rtx_scene_last_error", "rtx_frame_setup", "rtx_tiff_write", "rtx_hash_djb",
                      "rtx_params_from_argv", "rtx_stl_write", "rtx_tiff_read_raw", "rtx_buffer_free",
@@ -504,6 +520,27 @@ def declare_rtx(lib):
     lib.rtx_frame_features_device.restype = C.c_int
     lib.rtx_frame_features.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p]
     lib.rtx_frame_features.restype = C.c_int
+    lib.rtx_render_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
+    lib.rtx_render_rays.restype = C.c_int
+    lib.rtx_render_rays_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Params), C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+    lib.rtx_render_rays_device.restype = C.c_int
+    lib.rtx_ray_features.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rtx_ray_features.restype = C.c_int
+    lib.rtx_ray_features_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rtx_ray_features_device.restype = C.c_int
+    lib.rtx_projection_default.argtypes = [C.POINTER(Projection)]
+    lib.rtx_projection_default.restype = None
+    lib.rtx_projection_ray.argtypes = [C.POINTER(Frame), C.POINTER(Projection), C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.rtx_projection_ray.restype = C.c_int
+    lib.rtx_projection_rays_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Projection), C.c_void_p, C.c_void_p]
+    lib.rtx_projection_rays_device.restype = C.c_int
+    lib.rtx_render_projection.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Projection), C.POINTER(Params), C.c_void_p,
+                                          C.c_void_p]
+    lib.rtx_render_projection.restype = C.c_int
+    lib.rtx_render_projection_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.POINTER(Projection), C.POINTER(Params),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_render_projection_device.restype = C.c_int
     lib.rtx_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
     lib.rtx_denoise_params_default.restype = None
     lib.rtx_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p,

@@ -1188,6 +1188,89 @@ typedef struct rtx_temporal_stats {   /* the last rtx_temporal* or rtx_render_te
 int rtx_get_temporal_stats(const rtx_ctx *ctx, rtx_temporal_stats *out);
 
 /*
+ * A frame whose primary rays are the caller's: the renderer's whole shading (ray trees, path GI,
+ * area lights) behind any camera.  rays: width * height rtx_ray records, row-major, row 0 = top; pixel (px, py)
+ * traces record py * width + px from its origin along its dir, and everything after that ray is rtx_render's:
+ * the pixel's RNG key is (seed, py * width + px), so a pixel's value depends on its own record, its index and the
+ * parameters alone, never on its neighbours' records.  Of the frame's own rays (rtx_frame_rays_device) the image is
+ * rtx_render's bit for bit, rgb and z.  A record follows rtx_ray, with these rules for a primary ray:
+ *   hole       tmax of 0, a negative value or -INFINITY: nothing is traced or counted, the pixel is rgb 0 and z 0;
+ *   unbounded  every other tmax, a finite positive one, INFINITY and NaN alike: a primary ray is not clipped
+ *              (clipping at a finite tmax is not built);
+ *   NaN dir    a NaN direction component is a traced miss (rgb 0, z 0, one closest ray), as in rtx_trace_rays.
+ * dir is unit length, the caller's duty (z is in units of |dir|).
+ * The call honours tile_offset / tile_stride and fills rtx_get_stats and the per-feature statistics as rtx_render
+ * does.  It leaves the next rtx_render's chunk sizing as it was (the estimate is keyed by a camera, which a batch
+ * has not); its own chunks take the static bound, and the overflow retry.
+ * HOST buffers; rgb[W*H*3] and z[W*H] may each be NULL.  RTX_ERR_STATE before an upload; RTX_ERR_ARG for a null
+ * context, rays or params, a zero dimension, width * height > RTX_RAYS_MAX, bad tile sharding, max_bounces above the
+ * limit.  Not covered: device groups; tile lists, adaptive, multi-pass, filtered, upsampled and temporal renders of
+ * a batch; a finite primary tmax.
+ */
+int rtx_render_rays(rtx_ctx *ctx, uint32_t width, uint32_t height, const rtx_ray *rays, const rtx_params *params, float *rgb,
+		    float *z);
+/* Same on DEVICE buffers (d_rays 16-byte aligned; d_rgb / d_z may each be NULL), enqueued on `stream` (NULL = the
+ * context's own); synchronises the stream. */
+int rtx_render_rays_device(rtx_ctx *ctx, uint32_t width, uint32_t height, const void *d_rays, const rtx_params *params,
+			   void *d_rgb, void *d_z, void *stream);
+/* rtx_frame_features* with the caller's rays in place of the frame's own: a closest query of the batch (the ray
+ * queries' kernel), then the records.  A hole gives a miss record; on a batch of unbounded rays z is
+ * rtx_render_rays' z bit for bit (max_bounces >= 1).  (The query is rtx_trace_rays': a finite positive tmax does
+ * clip here.)  Errors as rtx_frame_features*, with the batch's size for the frame's. */
+int rtx_ray_features(rtx_ctx *ctx, uint32_t width, uint32_t height, const rtx_ray *rays, int32_t u32conv,
+		     rtx_feature *features);
+int rtx_ray_features_device(rtx_ctx *ctx, uint32_t width, uint32_t height, const void *d_rays, int32_t u32conv,
+			    void *d_features, void *stream);
+
+/*
+ * Camera models on top of it: a panoramic, a fisheye and an orthographic camera that looks where the pinhole
+ * rtx_frame looks.  From the frame, in double:
+ *     r = unit(step_x),  dn = unit(step_y),  f = +-(r x dn), the sign such that
+ *     f . (corner + (W/2) step_x + (H/2) step_y - origin) > 0
+ * (RTX_ERR_ARG for a step of zero length, for |r . dn| > 1e-3, which is no rectangle, and for an origin in the image
+ * plane).  With u = (px + 1/2 + offset_x) / W and v = (py + 1/2 + offset_y) / H:
+ *   RTX_PROJ_PANORAMA (equirectangular), fov in (0, 2 pi], the angle across the width:
+ *     lambda = (u - 1/2) fov,   phi = (1/2 - v) pi (fov / (2 pi)) (2 H / W);   |phi| > pi/2: a hole
+ *     d = cos phi (sin lambda r + cos lambda f) - sin phi dn,   origin = the frame's
+ *     (a 2:1 image at fov 2 pi spans the full sphere)
+ *   RTX_PROJ_FISHEYE (equidistant), fov in (0, 2 pi], the full angle across the width:
+ *     x = 2u - 1,  y = (2v - 1) H / W,  rho = sqrt(x^2 + y^2),  theta = rho fov / 2;   theta > pi: a hole
+ *     d = cos theta f + sin theta (x r + y dn) / rho,   d = f at rho = 0,   origin = the frame's
+ *   RTX_PROJ_ORTHO:
+ *     d = f,   origin = origin + (u - 1/2) E r + (v - 1/2) E (H / W) dn,
+ *     E = extent, the width of the view in scene units; 0: the image plane's own width W |step_x|
+ * Every formula is evaluated in double and each component rounded once to float; a ray has tmax = INFINITY, a hole is
+ * an all-zero record (tmax 0).  offset_x / offset_y are sub-pixel offsets in pixels: a caller anti-aliases by moving
+ * them and averaging renders of different seeds (rtx_render_passes does not do it for a projection).
+ * (2 pi rounded to float, the default fov, lies just above 2 pi and is accepted.)
+ */
+enum { RTX_PROJ_PANORAMA = 0, RTX_PROJ_FISHEYE = 1, RTX_PROJ_ORTHO = 2 };
+typedef struct rtx_projection {
+	int32_t kind;             /* RTX_PROJ_* */
+	float fov;                /* panorama, fisheye: radians, in (0, 2 pi] */
+	float extent;             /* ortho: E >= 0, finite */
+	float offset_x, offset_y; /* finite */
+} rtx_projection;
+/* panorama, fov 2 pi, extent 0, offsets 0 */
+void rtx_projection_default(rtx_projection *p);
+/* THE DEFINITION: pixel (px, py)'s ray by the formulas above, on the host, no device needed.  RTX_ERR_ARG for a null
+ * argument, a frame with a zero dimension or more than RTX_RAYS_MAX pixels or a non-finite field, the frame rules
+ * above, an unknown kind, a fov or extent outside its range, a non-finite offset, a pixel outside the frame. */
+int rtx_projection_ray(const rtx_frame *frame, const rtx_projection *proj, uint32_t px, uint32_t py, rtx_ray *out);
+/* The frame's width * height rays into a DEVICE buffer (16-byte aligned), formed by the device in double by the same
+ * text, enqueued on `stream` (NULL = the context's own); synchronises it.  Needs no uploaded scene.  Against
+ * rtx_projection_ray a component can differ by one float ulp, where the two doubles straddle a rounding boundary. */
+int rtx_projection_rays_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_projection *proj, void *d_rays, void *stream);
+/* The generator into a scratch buffer of the context, then rtx_render_rays_device: bit for bit what the two calls
+ * chained by hand give.  HOST buffers as rtx_render_rays.  Errors as the two calls, all but the sharding and
+ * max_bounces raised before anything is launched. */
+int rtx_render_projection(rtx_ctx *ctx, const rtx_frame *frame, const rtx_projection *proj, const rtx_params *params,
+			  float *rgb, float *z);
+/* Same into DEVICE buffers. */
+int rtx_render_projection_device(rtx_ctx *ctx, const rtx_frame *frame, const rtx_projection *proj, const rtx_params *params,
+				 void *d_rgb, void *d_z, void *stream);
+
+/*
  * Known-answer entry: evaluates one device function over n inputs on the GPU
  * (used by the -m gpu parity tests against the oracle's KAT fixtures).
  * kind / record layouts are listed in rtx_kat.h.
