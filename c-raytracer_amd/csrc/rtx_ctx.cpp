@@ -105,7 +105,7 @@ extern "C" int rtx_open(int device, rtx_ctx **out)
 	 * ~30 ms inside the first BVH build), and the runtime's pageable-copy path primed */
 	for (hipError_t (*load)(void) : { rtx_load_build, rtx_load_wide8_dev, rtx_load_shadow, rtx_load_trace, rtx_load_sort,
 					  rtx_load_post, rtx_load_gather, rtx_load_denoise, rtx_load_denoise_variance, rtx_load_passes,
-					  rtx_load_adaptive, rtx_load_filter, rtx_load_upsample, rtx_load_temporal, rtx_load_projection })
+					  rtx_load_adaptive, rtx_load_filter, rtx_load_upsample, rtx_load_temporal, rtx_load_projection, rtx_load_nearest })
 		if ((e = load()) != hipSuccess) {
 			rtx_close(c);
 			return fail(RTX_ERR_HIP, "loading the device code failed: %s", hipGetErrorString(e));
@@ -317,6 +317,7 @@ extern "C" int rtx_get_shadow_ray_stats(const rtx_ctx *c, rtx_shadow_ray_stats *
 {
 	return get_stats(c, &rtx_ctx::shadow_ray_stats, out);
 }
+extern "C" int rtx_get_closest_stats(const rtx_ctx *c, rtx_closest_stats *out) { return get_stats(c, &rtx_ctx::closest_stats, out); }
 extern "C" int rtx_get_denoise_stats(const rtx_ctx *c, rtx_denoise_stats *out) { return get_stats(c, &rtx_ctx::dn_stats, out); }
 extern "C" int rtx_get_pass_stats(const rtx_ctx *c, rtx_pass_stats *out) { return get_stats(c, &rtx_ctx::pass_stats, out); }
 extern "C" int rtx_get_adaptive_stats(const rtx_ctx *c, rtx_adaptive_stats *out) { return get_stats(c, &rtx_ctx::ad_stats, out); }

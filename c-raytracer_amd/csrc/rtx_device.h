@@ -395,4 +395,17 @@ enum {
 };
 static_assert(RTX_SQ_N <= RTX_RQ_HEADS, "the shadow-ray counters live in the ray queries' buffer");
 
+/* counters of a closest-point query (k_nearest, rtx_closest_points*), in the ray queries' buffer; the packet
+ * queue heads are k_rays' (RTX_RQ_HEADS) */
+enum {
+	RTX_NQ_FOUND = 0, /* points with an answer */
+	RTX_NQ_FAR,       /* points far from the bounded objects (rtx_math.h tf_far) */
+	RTX_NQ_NODES,     /* RTX_CLOSEST_COUNT: node visits, distance-function calls per object type */
+	RTX_NQ_TRIS,
+	RTX_NQ_SPHERES,
+	RTX_NQ_PLANES,
+	RTX_NQ_N
+};
+static_assert((int)RTX_NQ_N <= (int)RTX_RQ_HEADS,"the closest-point counters live in the ray queries' buffer");
+
 #endif

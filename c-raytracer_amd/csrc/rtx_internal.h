@@ -1,7 +1,7 @@
 /*
  * Library-internal declarations shared by the host files of the C-ABI: rtx_ctx.cpp (context,
  * options, statistics), rtx_scene.cpp (flattening, BVH builds), rtx_upload.cpp, rtx_render.cpp,
- * rtx_query.cpp (ray and shadow queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
+ * rtx_query.cpp (ray and shadow queries), rtx_nearest.cpp (closest-point queries), rtx_image.cpp (postprocess, feature buffers, denoiser),
  * rtx_passes.cpp (multi-pass rendering, adaptive passes), rtx_upsample.cpp (feature-guided upsampling), rtx_temporal.cpp (temporal accumulation), rtx_group.cpp (multi-device) and rtx_group_passes.cpp (multi-pass rendering on a group).  The device context, its scratch buffers' owner type, a
  * host-built scene, and the steps more than one of the files takes.
  * Not installed; nothing outside librtx includes it.
@@ -210,6 +210,7 @@ struct rtx_ctx : CtxHandles {
 	DevBuf<float4> d_qrays, d_qhits;
 	rtx_ray_stats ray_stats{};
 	rtx_shadow_ray_stats shadow_ray_stats{}; /* rtx_trace_shadow_rays */
+	rtx_closest_stats closest_stats{};       /* rtx_closest_points* */
 	/* denoiser (rtx_frame_features*, rtx_denoise*): grow-only scratch of its own */
 	DevBuf<float4> d_dn_rays, d_dn_hits; /* the frame's rays and their closest hits */
 	DevBuf<float4> d_dn_work;            /* the filter's 16-byte records (rtx_launch_denoise, rtx_launch_denoise_variance) */

@@ -98,7 +98,25 @@ hipError_t rtx_raysort_temp_bytes(uint32_t n, size_t *bytes);
 hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const float lo[3], const float hi[3], uint32_t *keys0,
 			      uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp, size_t temp_bytes,
 			      const uint32_t **perm, hipStream_t stream);
+/* ... and the closest-point queries' (RTX_CLOSEST_REORDER): points: n rtx_point_query records */
+hipError_t rtx_pointsort_temp_bytes(uint32_t n, size_t *bytes);
+hipError_t rtx_launch_pointsort(const float4 *points, uint32_t n, const float lo[3], const float hi[3], uint32_t *keys0,
+				uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp, size_t temp_bytes,
+				const uint32_t **perm, hipStream_t stream);
 RTX_HIDDEN hipError_t rtx_load_sort(void);
+
+/* rtx_nearest.hip: k_nearest (rtx_closest_points*) and the distance functions' known answers.  wmag: the largest
+ * coordinate magnitude of the bounded objects' world box; the lane stack is k_rays' (S->ostk sized for THIS grid) */
+size_t rtx_nearest_lds_bytes(uint32_t stack_size);
+hipError_t rtx_nearest_occupancy(uint32_t stack_size, int *blocks_per_cu);
+hipError_t rtx_launch_nearest(const DScene *S, const float4 *queries, float4 *results, const uint32_t *perm, uint32_t n,
+			      uint32_t queues, uint32_t grab, float wmag, int bounded_only, unsigned long long *ctr,
+			      uint32_t waves, int count, hipStream_t stream);
+hipError_t rtx_launch_nearest_kat(const rtx_object *objs, const uint32_t *index, const float *pts, uint64_t n, float4 *out,
+				  hipStream_t stream);
+hipError_t rtx_launch_nearest_grid(const rtx_object *objs, uint32_t n_obj, const float *pts, uint32_t n_pts, float *dist,
+				   hipStream_t stream);
+RTX_HIDDEN hipError_t rtx_load_nearest(void);
 
 /* rtx_post.hip */
 hipError_t rtx_launch_post(uint32_t w, uint32_t h, const rtx_post *pp, float *rgb, const float *z, int *rad, float4 *pv,

@@ -135,6 +135,58 @@ extern "C" hipError_t rtx_launch_raysort(const float4 *rays, uint32_t n, const f
 	return e;
 }
 
+/*
+ * Point-batch ordering for k_nearest (RTX_CLOSEST_REORDER): a caller's points sorted by the cell they
+ * lie in, so a packet's 64 lanes search one part of the tree.  Key: the 30-bit Morton code of the
+ * point in the bounded objects' box (10 bits per axis, clamped: points outside it land on its faces).
+ * As above, order changes which lane answers a point, never its answer.
+ */
+__global__ __launch_bounds__(256) void k_pointkey(const float4 *__restrict__ points, uint32_t n, float lox, float loy,
+						   float loz, float sx, float sy, float sz, uint32_t *__restrict__ keys,
+						   uint32_t *__restrict__ vals)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (j >= n)
+		return;
+	const float4 q = points[j];
+	/* NaN coordinates land in cell 0 (fmaxf / fminf return the other operand) */
+	const float x = fminf(fmaxf((q.x - lox) * sx, 0.f), 1023.f);
+	const float y = fminf(fmaxf((q.y - loy) * sy, 0.f), 1023.f);
+	const float z = fminf(fmaxf((q.z - loz) * sz, 0.f), 1023.f);
+	keys[j] = spread10((uint32_t)x) | (spread10((uint32_t)y) << 1) | (spread10((uint32_t)z) << 2);
+	vals[j] = (uint32_t)j;
+}
+
+extern "C" hipError_t rtx_pointsort_temp_bytes(uint32_t n, size_t *bytes)
+{
+	hipcub::DoubleBuffer<uint32_t> k(nullptr, nullptr), v(nullptr, nullptr);
+	return hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, k, v, (int)n, 0, 30);
+}
+
+/* points: n rtx_point_query records; keys / vals: two buffers of n each; *perm <- the sorted point indices */
+extern "C" hipError_t rtx_launch_pointsort(const float4 *points, uint32_t n, const float lo[3], const float hi[3],
+					   uint32_t *keys0, uint32_t *keys1, uint32_t *vals0, uint32_t *vals1, void *temp,
+					   size_t temp_bytes, const uint32_t **perm, hipStream_t stream)
+{
+	*perm = vals0;
+	if (!n)
+		return hipSuccess;
+	float s[3];
+	for (int a = 0; a < 3; a++) {
+		const float ext = hi[a] - lo[a];
+		s[a] = ext > 0.f ? 1024.f / ext : 0.f;
+	}
+	hipLaunchKernelGGL(k_pointkey, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, points, n, lo[0], lo[1],
+			   lo[2], s[0], s[1], s[2], keys0, vals0);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess)
+		return e;
+	hipcub::DoubleBuffer<uint32_t> k(keys0, keys1), v(vals0, vals1);
+	e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k, v, (int)n, 0, 30, stream);
+	*perm = v.Current();
+	return e;
+}
+
 /* the code object of this file on the current device, loaded now (rtx_open) rather than at the
  * first launch inside an upload or a render */
 extern "C" __attribute__((visibility("hidden"))) hipError_t rtx_load_sort(void)

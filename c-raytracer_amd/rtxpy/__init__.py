@@ -358,6 +358,34 @@ class Renderer:
         _check(self.lib.rtx_get_ray_stats(self._ctx, C.byref(s)))
         return s
 
+    def closest_points(self, points, max_dist=np.inf, bounded_only=False, reorder=False, count=False):
+        """rtx_closest_points on host arrays: points (n, 3), max_dist a scalar or (n,) (inf: unbounded).
+        Returns a dict of numpy arrays: dist (n,) float32 (inf on a miss), point (n, 3) float32 (0 on a miss),
+        object / material (n,) uint32 (abi.RTX_NONE on a miss)."""
+        points = np.asarray(points, np.float32).reshape(-1, 3)
+        n = points.shape[0]
+        q = np.zeros(n, abi.POINT_QUERY_DTYPE)
+        q["p"] = points
+        q["max_dist"] = np.asarray(max_dist, np.float32)
+        res = np.zeros(n, abi.CLOSEST_DTYPE)
+        flags = ((abi.RTX_CLOSEST_BOUNDED_ONLY if bounded_only else 0) | (abi.RTX_CLOSEST_REORDER if reorder else 0)
+                 | (abi.RTX_CLOSEST_COUNT if count else 0))
+        _check(self.lib.rtx_closest_points(self._ctx, n, q.ctypes.data if n else None, res.ctypes.data if n else None,
+                                           flags))
+        return {k: res[k].copy() for k in ("dist", "point", "object", "material")}
+
+    def closest_points_device(self, n, queries_ptr, results_ptr, flags=0, stream=None):
+        """rtx_closest_points_device: queries_ptr / results_ptr are device pointers (ints, e.g. a torch tensor's
+        data_ptr()) to n rtx_point_query (4 float32 words) / rtx_closest (8 words) records; stream: hipStream_t
+        as int or None."""
+        _check(self.lib.rtx_closest_points_device(self._ctx, n, C.c_void_p(queries_ptr), C.c_void_p(results_ptr), flags,
+                                                  C.c_void_p(stream) if stream else None))
+
+    def closest_stats(self):
+        s = abi.ClosestStats()
+        _check(self.lib.rtx_get_closest_stats(self._ctx, C.byref(s)))
+        return s
+
     def shadow_rays(self, origins, dirs, dist, light_object=-1, slots=False, count=False):
         """rtx_trace_shadow_rays on host arrays: origins / dirs (n, 3), dist and light_object a scalar or (n,).
         Ray i runs in lane i % 64 of packet i / 64.  Returns a dict of numpy arrays: blocked (n,) bool,
@@ -964,6 +992,46 @@ def gpu_kat(kind, records, params=None):
     out = np.zeros((records.shape[0], abi.KAT_OUT[kind]), np.float32)
     p = params or default_params()
     _check(rtx_lib().rtx_kat(kind, records.shape[0], records.ctypes.data, out.ctypes.data, C.byref(p)))
+    return out
+
+
+def closest_point_object(scene, object_index, P):
+    """rtx_closest_point_object, the definition of the closest-point queries, on the host: (dist, cp (3,) float32) of
+    object `object_index` of the scene and the point P"""
+    if not 0 <= object_index < scene.desc.num_objects:
+        raise IndexError("object index out of range")
+    p = np.ascontiguousarray(P, dtype=np.float32).reshape(3)
+    dist = C.c_float()
+    cp = np.zeros(3, np.float32)
+    _check(rtx_lib().rtx_closest_point_object(C.addressof(scene.desc.objects[object_index]), p.ctypes.data, C.byref(dist),
+                                              cp.ctypes.data))
+    return np.float32(dist.value), cp
+
+
+def closest_kat(objects, object_index, points):
+    """rtx_closest_kat: the device's distance functions on (object, point) pairs, no search.  objects: a numpy
+    array of rtx_object records (abi.Object's layout); object_index (n,) or None (pair i = object i); points (n, 3).
+    Returns (dist (n,), cp (n, 3))."""
+    objects = np.ascontiguousarray(objects)
+    assert objects.dtype.itemsize == C.sizeof(abi.Object)
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = points.shape[0]
+    idx = None if object_index is None else np.ascontiguousarray(object_index, dtype=np.uint32)
+    assert idx is None or idx.shape == (n,)
+    out = np.zeros((n, 4), np.float32)
+    _check(rtx_lib().rtx_closest_kat(len(objects), objects.ctypes.data, n, None if idx is None else idx.ctypes.data,
+                                     points.ctypes.data, out.ctypes.data))
+    return out[:, 0].copy(), out[:, 1:].copy()
+
+
+def closest_kat_grid(objects, points):
+    """rtx_closest_kat_grid: dist (n_points, n_objects) float32 of every object to every point, on the device"""
+    objects = np.ascontiguousarray(objects)
+    assert objects.dtype.itemsize == C.sizeof(abi.Object)
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((points.shape[0], len(objects)), np.float32)
+    _check(rtx_lib().rtx_closest_kat_grid(len(objects), objects.ctypes.data, points.shape[0], points.ctypes.data,
+                                          out.ctypes.data))
     return out
 
 

@@ -178,6 +178,29 @@ class ShadowRayStats(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+# closest-point queries (rtx_closest_points*)
+RTX_CLOSEST_BOUNDED_ONLY, RTX_CLOSEST_REORDER, RTX_CLOSEST_COUNT = 1, 2, 4
+RTX_NONE = 0xFFFFFFFF
+
+
+class PointQuery(C.Structure):
+    _fields_ = [("p", F3), ("max_dist", C.c_float)]
+
+
+class Closest(C.Structure):
+    _fields_ = [("point", F3), ("dist", C.c_float), ("object", C.c_uint32), ("material", C.c_uint32),
+                ("pad", C.c_uint32 * 2)]
+
+
+class ClosestStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64),
+                ("sphere_tests", C.c_uint64), ("plane_tests", C.c_uint64), ("far_points", C.c_uint64),
+                ("kernel_ms", C.c_double), ("sort_ms", C.c_double)]
+
+
+POINT_QUERY_DTYPE = [("p", "<f4", 3), ("max_dist", "<f4")]
+CLOSEST_DTYPE = [("point", "<f4", 3), ("dist", "<f4"), ("object", "<u4"), ("material", "<u4"), ("pad", "<u4", 2)]
+
 SHADOW_RAY_DTYPE = [("origin", "<f4", 3), ("dist", "<f4"), ("dir", "<f4", 3), ("light_object", "<i4")]
 SHADOW_RESULT_DTYPE = [("transmittance", "<f4", 3), ("blocked", "<u4")]
 
@@ -338,6 +361,8 @@ RTX_SYMBOLS = ["rtx_params_default", "rtx_device_count", "rtx_open", "rtx_upload
                "rtx_tile_pack_device", "rtx_tile_unpack_device", "rtx_tree_frame",
                "rtx_trace_rays", "rtx_trace_rays_device", "rtx_frame_rays_device", "rtx_get_ray_stats",
                "rtx_trace_shadow_rays", "rtx_get_shadow_ray_stats",
+               "rtx_closest_point_object", "rtx_closest_points", "rtx_closest_points_device", "rtx_get_closest_stats",
+               "rtx_closest_kat", "rtx_closest_kat_grid",
                "rtx_frame_features_device", "rtx_frame_features", "rtx_denoise_params_default", "rtx_denoise_device",
                "rtx_denoise", "rtx_get_denoise_stats",
                "rtx_denoise_variance_params_default", "rtx_denoise_variance_device", "rtx_denoise_variance",
@@ -516,6 +541,18 @@ def declare_rtx(lib):
     lib.rtx_trace_shadow_rays.restype = C.c_int
     lib.rtx_get_shadow_ray_stats.argtypes = [C.c_void_p, C.POINTER(ShadowRayStats)]
     lib.rtx_get_shadow_ray_stats.restype = C.c_int
+    lib.rtx_closest_point_object.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_closest_point_object.restype = C.c_int
+    lib.rtx_closest_points.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.rtx_closest_points.restype = C.c_int
+    lib.rtx_closest_points_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.rtx_closest_points_device.restype = C.c_int
+    lib.rtx_get_closest_stats.argtypes = [C.c_void_p, C.POINTER(ClosestStats)]
+    lib.rtx_get_closest_stats.restype = C.c_int
+    lib.rtx_closest_kat.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtx_closest_kat.restype = C.c_int
+    lib.rtx_closest_kat_grid.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.rtx_closest_kat_grid.restype = C.c_int
     lib.rtx_frame_features_device.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p]
     lib.rtx_frame_features_device.restype = C.c_int
     lib.rtx_frame_features.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p]

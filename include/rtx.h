@@ -520,6 +520,78 @@ typedef struct rtx_shadow_ray_stats { /* the last rtx_trace_shadow_rays of the c
 int rtx_get_shadow_ray_stats(const rtx_ctx *ctx, rtx_shadow_ray_stats *out);
 
 /*
+ * Closest-point queries: the nearest surface point of the uploaded scene to each of a caller's points,
+ * and how far it is.
+ *
+ * THE DEFINITION is rtx_closest_point_object: the distance from a point P to ONE object and that
+ * object's closest point cp, in float32 with a fixed operation order (csrc/rtx_nearest_math.h, the one
+ * text the host and the device compile, so both return the same bits):
+ *   triangle  the closest point of the closed triangle p0, p0 + e1, p0 + e2 (the record's vertex and
+ *             edges): the closest points of its three edge segments (the clamp of a segment's
+ *             parameter gives the vertex regions) and, where the foot of the perpendicular lies in the
+ *             triangle, that foot; the candidate of least squared distance, dist = sqrtf of it.  A
+ *             zero-area triangle gives the closest point of the segment or point it collapses to;
+ *             never NaN.
+ *   sphere    dist = | |P - c| - r |, cp = c + (P - c) (r / |P - c|); P == c: cp = c + (r, 0, 0)
+ *   plane     dist = | n . P - d |, cp = P - (n . P - d) n
+ * It touches no device and needs no context.  RTX_ERR_ARG for a null pointer or an unknown type.
+ */
+int rtx_closest_point_object(const rtx_object *obj, const float P[3], float *dist, float cp[3]);
+
+typedef struct rtx_point_query {  /* 16 B */
+	float p[3];               /* a NaN or infinite coordinate = a miss */
+	float max_dist;           /* answers need dist < max_dist, strictly: an answer's own dist excludes it, the next
+	                           * float above keeps it; INFINITY (or NaN) = unbounded; 0, a negative value or
+	                           * -INFINITY = a miss */
+} rtx_point_query;
+typedef struct rtx_closest {      /* 32 B */
+	float point[3];           /* the reported object's cp; 0 on a miss */
+	float dist;               /* the least dist over the scene's objects; INFINITY on a miss */
+	uint32_t object;          /* index into rtx_scene_desc.objects; RTX_NONE on a miss */
+	uint32_t material;        /* index into rtx_scene_desc.materials; RTX_NONE on a miss */
+	uint32_t pad[2];          /* 0 */
+} rtx_closest;
+#ifndef RTX_NONE
+#define RTX_NONE 0xFFFFFFFFu
+#endif
+enum {
+	RTX_CLOSEST_BOUNDED_ONLY = 1, /* leave the planes out */
+	RTX_CLOSEST_REORDER = 2,      /* sort the batch by the point's cell first (30-bit Morton code of the point in
+	                               * the bounded objects' box); results land in input order */
+	RTX_CLOSEST_COUNT = 4         /* fill the traversal counters of rtx_closest_stats (counting kernel instance) */
+};
+/* n queries from / results to HOST buffers.  A query's answer is the object of least dist (the definition's)
+ * among those with dist < max_dist.  dist never depends on the batch a point is in, its order or
+ * RTX_CLOSEST_REORDER (it is a minimum over the objects the search did not prune, and the search prunes only
+ * what a deflated lower bound proves farther); object may differ between two orders only where two objects'
+ * functions return the very same dist (the first one found keeps it); point is the reported object's cp.
+ * Errors as rtx_trace_rays: n == 0 returns RTX_OK and launches nothing; RTX_ERR_STATE before an upload;
+ * RTX_ERR_ARG for a null context, a null buffer with n > 0, unknown flag bits or n > RTX_RAYS_MAX.  Like a ray
+ * query it renders nothing, leaves rtx_get_stats and the next render as they were, and shares (and may grow) the
+ * context's scratch buffers. */
+int rtx_closest_points(rtx_ctx *ctx, uint64_t n, const rtx_point_query *queries, rtx_closest *results, uint32_t flags);
+/* Same on DEVICE buffers of the context's device (16-byte aligned, RTX_ERR_ARG otherwise), enqueued on
+ * `stream` (hipStream_t, NULL = the context's own); synchronises the stream.  results[n..] is not written. */
+int rtx_closest_points_device(rtx_ctx *ctx, uint64_t n, const void *d_queries, void *d_results, uint32_t flags, void *stream);
+typedef struct rtx_closest_stats { /* the last rtx_closest_points* of the context */
+	uint64_t points, found;
+	/* only with RTX_CLOSEST_COUNT: node visits of the search, distance-function calls per object type */
+	uint64_t node_visits, tri_tests, sphere_tests, plane_tests;
+	uint64_t far_points;      /* points far from the bounded objects (more than 4 radii from their centre) */
+	double kernel_ms;         /* k_nearest, HIP events */
+	double sort_ms;           /* RTX_CLOSEST_REORDER: key kernel + radix sort (else 0) */
+} rtx_closest_stats;
+int rtx_get_closest_stats(const rtx_ctx *ctx, rtx_closest_stats *out);
+/* Known answers of the definition on the DEVICE, without any search (the tests hold the kernel's search and
+ * its arithmetic apart with them).  Host buffers; the first device.  rtx_closest_kat: pair i is object
+ * object_index[i] (i itself where object_index is NULL) of objects[n_objects] and point points[3 i ..];
+ * out[4 i ..] = dist, cp.  rtx_closest_kat_grid: every object to every point, dist[p * n_objects + o].
+ * RTX_ERR_ARG for a null buffer, an index out of range or more than RTX_RAYS_MAX pairs. */
+int rtx_closest_kat(uint32_t n_objects, const rtx_object *objects, uint64_t n, const uint32_t *object_index,
+		    const float *points, float *out);
+int rtx_closest_kat_grid(uint32_t n_objects, const rtx_object *objects, uint32_t n_points, const float *points, float *dist);
+
+/*
  * Several devices rendering one frame (the reference's own parallel point is
  * the OpenMP row loop of render.c:349-352).  The group builds the scene's BVHs once, on its
  * first device (rtx_upload_scene's work: device SAH build, 8-wide collapse), and the other
