@@ -50,7 +50,7 @@ hipError_t rtx_w8_collapse_device(const DNode *recs, uint32_t nnodes, uint32_t n
 				  uint32_t *top_out, float qo[3], float qs[3], hipStream_t st);
 RTX_HIDDEN hipError_t rtx_load_wide8_dev(void);
 
-/* rtx_trace.hip: k_trace, k_accum, k_rays, the frame's rays.  tile_list: the device list of a tile-list render
+/* rtx_trace.hip (defined in its part rtx_trace_launch.h): k_trace, k_accum, k_rays, the frame's rays.  tile_list: the device list of a tile-list render
  * (rtx_render_tiles*), indexed by the chunk positions tile_begin..; null: the shard of P.  pack: the packed GI
  * walk's region (RTX_OPT_TRACE_PACK), waves * rtx_trace_pack_bytes(pack_seg) bytes, for a scene that walks the
  * 8-wide tree (S->trace_w8); null: every GI batch walks on its own.  prim_rays: the F->width * F->height rtx_ray

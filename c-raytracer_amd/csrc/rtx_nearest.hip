@@ -21,6 +21,7 @@
 
 #include "rtx.h"
 #include "rtx_device.h"
+#include "rtx_lane_stack.h"
 #include "rtx_launch.h"
 #include "rtx_math.h"
 #include "rtx_nearest_math.h"
@@ -100,30 +101,9 @@ template <int C> __device__ __forceinline__ float near_child(const uint32_t (&w)
 	return sqrtf(gx * gx + gy * gy + gz * gz);
 }
 
-/* the lane stack, sized as k_rays sizes its own: the first RTX_TRACE_LSTK entries in LDS, the rest in
- * HBM [entry][grid lane]; cap = DScene.stack_size entries in all.  A push beyond cap is refused (no
- * tree is that deep: one entry per level at most), never written. */
-struct NearStack {
-	lds_u32 *ls;
-	uint32_t *os;
-	size_t ostride;
-	uint32_t cap, sp;
-	__device__ __forceinline__ void push(uint32_t v)
-	{
-		if (sp >= cap)
-			return;
-		if (sp < RTX_TRACE_LSTK)
-			ls[sp * WAVE + lane_id()] = v;
-		else
-			os[(sp - RTX_TRACE_LSTK) * ostride + lane_id()] = v;
-		sp++;
-	}
-	__device__ __forceinline__ uint32_t pop()
-	{
-		sp--;
-		return sp < RTX_TRACE_LSTK ? ls[sp * WAVE + lane_id()] : os[(sp - RTX_TRACE_LSTK) * ostride + lane_id()];
-	}
-};
+/* the lane stack, sized as k_rays sizes its own (rtx_lane_stack.h), with the capacity check: DScene.stack_size
+ * entries in all */
+typedef LaneStack<true> NearStack;
 
 /*
  * Best-first search of the 8-wide tree.  A node visit forms the eight bounds, tests the leaf slots
@@ -266,7 +246,7 @@ __device__ __forceinline__ void near_walk2(const DScene &S, NearStack &stk, cons
 	}
 }
 
-/* Persistent waves and packet queues as k_rays (rtx_trace.hip): wave b takes `grab` consecutive
+/* Persistent waves and packet queues as k_rays (rtx_trace_rays.h): wave b takes `grab` consecutive
  * 64-point packets at a time from queue b % queues.  A query is one float4 (rtx_point_query: p,
  * max_dist), a result two (rtx_closest: point, dist | object, material, 0, 0).  With perm (the
  * RTX_CLOSEST_REORDER sort's index list) lane i of a packet answers query perm[i]. */
@@ -344,12 +324,7 @@ __global__ __launch_bounds__(WAVE) void k_nearest(DScene S, const float4 *__rest
 				n_far++;
 			const float mag = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), wmag));
 			const float slack = mag * 0x1p-16f;
-			NearStack stk;
-			stk.ls = (lds_u32 *)lds_raw;
-			stk.os = S.ostk + (size_t)blockIdx.x * WAVE;
-			stk.ostride = (size_t)gridDim.x * WAVE;
-			stk.cap = S.stack_size;
-			stk.sp = 0;
+			NearStack stk = lane_stack<true>(S, lds_raw);
 			if (S.w8)
 				near_walk8<COUNT>(S, stk, P, pb, slack, B, nc);
 			else

@@ -394,12 +394,9 @@ __device__ __forceinline__ uint32_t *w8_spill_at(const QBvh &Q, uint32_t k)
 	return Q.spill + ((size_t)(k - Q.lstk) * ((size_t)gridDim.x * B) + (size_t)blockIdx.x * B + Q.wv * WAVE + lane_id());
 }
 
-/* the visit order of hit children: plain slot order (RTX_W8_SORDER 0), front to back from the
- * shade point (1), or front to back from the light (2) */
-template <int OCT> __device__ __forceinline__ constexpr uint32_t w8_sorder()
-{
-	return (OCT == 8 || !RTX_W8_SORDER) ? 0u : RTX_W8_SORDER == 2 ? ((uint32_t)OCT & 7u) : (~(uint32_t)OCT & 7u);
-}
+/* the visit order of hit children (slot p ^ W8_SORDER): plain slot order.  Fixed: front to back from the
+ * shade point or from the light measured no faster (scene5 567.3 against 577.2 / 575.5 ms) */
+constexpr uint32_t W8_SORDER = 0u;
 
 /* one lane's 8-wide any-hit walk: the node it is at (RTX_NONE: no node work), the kept sibling
  * group and the stack depth below it, the deferred transparent-leaf group and the queue depth */
@@ -440,7 +437,7 @@ template <bool COUNT, int OCT, bool LA>
 __device__ __forceinline__ void w8_iter(const QBvh &Q, f3 o, f3 d, f3 invq, f3 oi, float &tl, f3 &li, W8Walk &w, W8Ctr &c,
 					bool wk, bool hd, u64 walking, u64 holding)
 {
-	constexpr uint32_t K = w8_sorder<OCT>();
+	constexpr uint32_t K = W8_SORDER;
 	lds_u32 *stk = Q.stk, *tq = Q.tq;
 	if (!walking || popc64(holding) >= RTX_W8_DEFER || ballot(w.tn == RTX_W8_TQ)) {
 		/* a round of deferred transparent-leaf tests */

@@ -17,13 +17,20 @@
  *           contiguous array at tile end.
  *  k_accum  (one wave per tile) adds the shade points' light terms, computed by
  *           k_shadow, to their pixels in emission order.
- *  k_rays   (persistent, one wave per workgroup; 64-ray packets from device queues) the
- *           closest or any hit of a caller's ray batch (rtx_trace_rays*), with k_trace's
- *           walks and hit records; k_frame_rays writes a frame's primary rays for it.
- *  k_kat    per-function known answers of the device intersectors/samplers.
  *
  * No float atomics anywhere: a pixel's value is bit-identical whichever wave,
  * GPU or tile order renders it.
+ *
+ * This file holds everything compiled into a k_trace or k_accum instance: the closest walks,
+ * hit_info, shade-point emission, the GI batches and the two kernels.  The rest of the
+ * translation unit (one object, because the device functions here are shared) is included at
+ * the end, a part each:
+ *   rtx_trace_rays.h    k_rays (persistent, one wave per workgroup; 64-ray packets from device
+ *                       queues): the closest or any hit of a caller's ray batch (rtx_trace_rays*),
+ *                       with k_trace's walks and hit records; k_frame_rays writes a frame's
+ *                       primary rays for it
+ *   rtx_trace_kat.h     k_kat: per-function known answers of the device intersectors / samplers
+ *   rtx_trace_launch.h  the host launch code
  */
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -32,7 +39,13 @@
 #include "rtx_kat.h"
 #include "rtx_wave.h"
 #include "rtx_w8.h"
+#include "rtx_lane_stack.h"
 #include "rtx_launch.h"
+
+/* The compile-time switch of this translation unit (rtx_device.h has the sizing constants the host reads too): */
+#ifndef RTX_TRACE_OCC
+#define RTX_TRACE_OCC 6 /* waves per SIMD k_trace is register-capped for (80 VGPRs; with 9 LDS stack entries, 24 waves per CU) */
+#endif
 
 /* ------------------------------------------------------------------------ */
 /* closest hit: inside-object shortcut, planes, then BVH (render.c:118-147)  */
@@ -104,23 +117,7 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 		}
 		const f3 oi = mul3v(ob, inv);
 		uint32_t ref = S.root_ref;
-		uint32_t sp = 0;
-		/* entries from RTX_TRACE_LSTK on live in HBM, [entry][grid lane]; lane addresses formed at
-		 * each use (lane_id), none kept live across the walk */
-		lds_u32 *ls = (lds_u32 *)stk;
-		uint32_t *ostk = S.ostk + (size_t)blockIdx.x * WAVE;
-		const size_t ostride = (size_t)gridDim.x * WAVE;
-		auto push = [&](uint32_t v) {
-			if (sp < RTX_TRACE_LSTK)
-				ls[sp * WAVE + lane_id()] = v;
-			else
-				ostk[(sp - RTX_TRACE_LSTK) * ostride + lane_id()] = v;
-			sp++;
-		};
-		auto pop = [&]() -> uint32_t {
-			sp--;
-			return sp < RTX_TRACE_LSTK ? ls[sp * WAVE + lane_id()] : ostk[(sp - RTX_TRACE_LSTK) * ostride + lane_id()];
-		};
+		LaneStack<false> st = lane_stack<false>(S, stk);
 		for (;;) {
 			if (ref & RTX_REF_LEAF) {
 				const uint32_t first = (ref & RTX_REF_OFF) / (uint32_t)sizeof(DNode) - S.num_nodes,
@@ -150,9 +147,9 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 				}
 				if (ANY && hid != RTX_NONE) /* a plane hit never enters the walk: this hit is the walk's */
 					break;
-				if (sp == 0)
+				if (st.sp == 0)
 					break;
-				ref = pop();
+				ref = st.pop();
 			} else {
 				const float4 *nd = (const float4 *)((const char *)S.nodes + (ref & RTX_REF_OFF));
 				const float4 n0 = nd[0], n1 = nd[1], n2 = nd[2];
@@ -166,16 +163,16 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
 				if (h0 && h1) {
 					/* nearer child first; tie -> right first (accel.c:341-345) */
 					const bool l_first = tn0 < tn1;
-					push(l_first ? n3.y : n3.x);
+					st.push(l_first ? n3.y : n3.x);
 					ref = l_first ? n3.x : n3.y;
 				} else if (h0) {
 					ref = n3.x;
 				} else if (h1) {
 					ref = n3.y;
 				} else {
-					if (sp == 0)
+					if (st.sp == 0)
 						break;
-					ref = pop();
+					ref = st.pop();
 				}
 			}
 		}
@@ -192,18 +189,9 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
  * groups on the lane's stack (LDS, deeper entries in HBM), and every node's boxes are tested
  * against the current closest t.  The emitters the tree leaves out (DScene.w8noemit) are
  * tested before the walk.  Strict < everywhere: the first hit found at the least t wins. */
-#ifndef RTX_TRACE_SCALAR
-#define RTX_TRACE_SCALAR 1 /* a step where every lane is at one node reads its scalar-path copy (rtx_device.h DW8S) */
-#endif
-#ifndef RTX_TRACE_NEAR
-#define RTX_TRACE_NEAR 1 /* closest hits: visit the nearest hit inner child first (scene6 k_trace 605 -> 417 ms) */
-#endif
-#ifndef RTX_TRACE_CULL
-#define RTX_TRACE_CULL 0 /* closest hits: drop kept sibling groups that start beyond the closest hit */
-#endif
-#ifndef RTX_TRACE_EMPTYCOUNT
-#define RTX_TRACE_EMPTYCOUNT 0 /* measurement builds: count only the visits that hit no child */
-#endif
+/* Fixed choices of the walk: a step where every lane is at one node reads its scalar-path copy (rtx_device.h
+ * DW8S); the nearest hit inner child is visited first (scene6 k_trace 605 -> 417 ms), the others in the
+ * octant's slot order; kept sibling groups are not dropped when the closest hit passes their entry distance. */
 /* FAR: some lane of the wave has a far origin (t0 and the per-lane far flag live across the walk);
  * the other instances take t0 = 0 and no far lane as constants, so the waves of near rays (all of
  * them in the reference scenes' views) keep those registers for the walk */
@@ -212,49 +200,24 @@ __device__ void trace_closest_bvh2(const DScene &S, uint32_t *stk, bool act, f3 
  * empty after a first visit); a walk entered at (node, grp) with the ray's tbest / hid so far is that
  * walk resumed.  The defaults are the whole walk from the root. */
 template <bool COUNT, int OCT, bool FAR, bool ANY = false, bool ONE = false>
-__device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uint32_t *ostk, size_t ostride, f3 o, f3 d,
-					      f3 ob, f3 inv, float t0_, bool far_, float &tbest, uint32_t &hid,
-					      TraceCount &tc, uint32_t node = 0, uint32_t grp = 0, uint2 *left = nullptr)
+__device__ __forceinline__ void closest_walk8(const DScene &S, LaneStack<false> st, f3 o, f3 d, f3 ob, f3 inv, float t0_,
+					      bool far_, float &tbest, uint32_t &hid, TraceCount &tc, uint32_t node = 0,
+					      uint32_t grp = 0, uint2 *left = nullptr)
 {
 	const float t0 = FAR ? t0_ : 0.f;
 	const bool far = FAR && far_;
-	/* the lane stack: stk / ostk are the wave's bases (LDS, then HBM [entry][grid lane]); a lane's
-	 * address is formed at each use (lane_id), none kept live across the walk */
-	uint32_t sp = 0;
-	auto push = [&](uint32_t v) {
-		if (sp < RTX_TRACE_LSTK)
-			stk[sp * WAVE + lane_id()] = v;
-		else
-			ostk[(sp - RTX_TRACE_LSTK) * ostride + lane_id()] = v;
-		sp++;
-	};
-	auto pop = [&]() -> uint32_t {
-		sp--;
-		return sp < RTX_TRACE_LSTK ? stk[sp * WAVE + lane_id()] : ostk[(sp - RTX_TRACE_LSTK) * ostride + lane_id()];
-	};
-	constexpr uint32_t K = (OCT == 8 || !RTX_W8_ORDER) ? 0u : (~(uint32_t)OCT & 7u);
+	constexpr uint32_t K = OCT == 8 ? 0u : (~(uint32_t)OCT & 7u);
 	/* ob / inv: the ray's origin and inverse direction in the trees' frame, ob at parameter t0 of
 	 * the world ray o / d (tf_shift; 0 unless the origin is far): boxes are tested against tbest - t0 */
 	const f3 qs = ld3(S.w8qs), qo = ld3(S.w8qo);
 	const f3 invq = mk3(inv.x / qs.x, inv.y / qs.y, inv.z / qs.z);
 	const f3 oq = mk3((ob.x - qo.x) * qs.x, (ob.y - qo.y) * qs.y, (ob.z - qo.z) * qs.z);
 	const f3 oi = mul3v(oq, invq);
-	float gt = -INFINITY; /* RTX_TRACE_CULL: least entry distance of the group in grp (-inf: unknown) */
-	constexpr bool T = RTX_TRACE_NEAR || RTX_TRACE_CULL;
 	while (node != RTX_NONE) {
-		W8Visit v;
-		uint32_t nearp = 8;
-		float tin = INFINITY;
+		W8VisitT r;
 		const uint32_t un = uni(node);
-		if (RTX_TRACE_SCALAR && !ballot(node != un)) {
-			if (T) {
-				const W8VisitT r = w8_visit_st<OCT, K>(S.w8s + (size_t)un, invq, oi, tbest - t0);
-				v = r.v;
-				nearp = r.near;
-				tin = r.tin;
-			} else {
-				v = w8_visit_s<OCT, K>(S.w8s + (size_t)un, invq, oi, tbest - t0);
-			}
+		if (!ballot(node != un)) {
+			r = w8_visit_st<OCT, K>(S.w8s + (size_t)un, invq, oi, tbest - t0);
 		} else {
 			uint32_t w[16];
 			const DW8 *N = S.w8 + (size_t)node;
@@ -266,16 +229,10 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 				w[4 * k + 2] = x.z;
 				w[4 * k + 3] = x.w;
 			}
-			if (T) {
-				const W8VisitT r = w8_visit_t<OCT, K>(w, invq, oi, tbest - t0);
-				v = r.v;
-				nearp = r.near;
-				tin = r.tin;
-			} else {
-				v = w8_visit<OCT, K, false>(w, invq, oi, tbest - t0);
-			}
+			r = w8_visit_t<OCT, K>(w, invq, oi, tbest - t0);
 		}
-		if (COUNT && (!RTX_TRACE_EMPTYCOUNT || !v.hm))
+		const W8Visit &v = r.v;
+		if (COUNT)
 			tc.nodes++;
 		uint32_t lm = v.hm & ~v.io, im = v.hm & v.io;
 		while (lm) {
@@ -302,33 +259,22 @@ __device__ __forceinline__ void closest_walk8(const DScene &S, lds_u32 *stk, uin
 					return;
 			}
 		}
-		if (RTX_TRACE_CULL && tin > tbest) /* every hit inner child starts beyond the closest hit */
-			im = 0;
 		if (im) {
-			const uint32_t p0 = (RTX_TRACE_NEAR && nearp < 8) ? nearp : (uint32_t)__builtin_ctz(im);
+			const uint32_t p0 = r.near < 8 ? r.near : (uint32_t)__builtin_ctz(im);
 			node = v.base + (p0 ^ K);
 			im &= ~(1u << p0);
 			if (im) {
 				if (grp)
-					push(grp);
+					st.push(grp);
 				grp = (v.base << 8) | im;
-				gt = tin;
 			}
+		} else if (grp) {
+			node = (grp >> 8) + (__builtin_ctz(grp) ^ K);
+			grp &= grp - 1;
+			if (!(grp & 0xFFu))
+				grp = st.sp ? st.pop() : 0u;
 		} else {
-			if (RTX_TRACE_CULL && grp && gt > tbest) { /* the kept group starts beyond the closest hit */
-				grp = sp ? pop() : 0u;
-				gt = -INFINITY;
-			}
-			if (grp) {
-				node = (grp >> 8) + (__builtin_ctz(grp) ^ K);
-				grp &= grp - 1;
-				if (!(grp & 0xFFu)) {
-					grp = sp ? pop() : 0u;
-					gt = -INFINITY;
-				}
-			} else {
-				node = RTX_NONE;
-			}
+			node = RTX_NONE;
 		}
 		if (ONE)
 			break;
@@ -422,31 +368,28 @@ __device__ void trace_closest_w8(const DScene &S, uint32_t *stk, bool act, f3 o,
 				}
 			}
 		}
-		lds_u32 *ls = (lds_u32 *)stk;
-		uint32_t *ostk = S.ostk + (size_t)blockIdx.x * WAVE;
-		const size_t ostride = (size_t)gridDim.x * WAVE;
+		const LaneStack<false> st = lane_stack<false>(S, stk);
 		const uint32_t oct = ((~__float_as_uint(inv.x)) >> 31) | (((~__float_as_uint(inv.y)) >> 31) << 1) |
 				     (((~__float_as_uint(inv.z)) >> 31) << 2);
 		const uint32_t lead = readlane(oct, (uint32_t)__ffsll((long long)live) - 1);
 		const uint32_t sel = ballot(act & (oct != lead)) ? 8u : lead;
 		const bool anyfar = ballot(far) != 0;
 		if (act && anyfar) {
-			closest_walk8<COUNT, 8, true, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
+			closest_walk8<COUNT, 8, true, ANY>(S, st, o, d, ob, inv, t0, far, tbest, hid, tc);
 		} else if (act) {
 			switch (sel) {
-#define RTX_CWALK(K)                                                                           \
-	case K:                                                                                    \
-		closest_walk8<COUNT, K, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc); \
+#define RTX_CWALK(K)                                                                   \
+	case K:                                                                            \
+		closest_walk8<COUNT, K, false, ANY>(S, st, o, d, ob, inv, t0, far, tbest, hid, tc); \
 		break;
 				RTX_CWALK(0) RTX_CWALK(1) RTX_CWALK(2) RTX_CWALK(3) RTX_CWALK(4) RTX_CWALK(5) RTX_CWALK(6)
 				RTX_CWALK(7)
 #undef RTX_CWALK
 			default:
 				if constexpr (ROOT)
-					closest_walk8<COUNT, 8, false, ANY, true>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest,
-										  hid, tc, 0u, 0u, left);
+					closest_walk8<COUNT, 8, false, ANY, true>(S, st, o, d, ob, inv, t0, far, tbest, hid, tc, 0u, 0u, left);
 				else
-					closest_walk8<COUNT, 8, false, ANY>(S, ls, ostk, ostride, o, d, ob, inv, t0, far, tbest, hid, tc);
+					closest_walk8<COUNT, 8, false, ANY>(S, st, o, d, ob, inv, t0, far, tbest, hid, tc);
 				break;
 			}
 		}
@@ -466,8 +409,7 @@ __device__ __forceinline__ void resume_closest_w8(const DScene &S, uint32_t *stk
 	const f3 ob = rot ? tf_point(S.tf.r, S.tf.c, o) : o;
 	const f3 inv = safe_inv_fast(rot ? tf_dir(S.tf.r, d) : d);
 	if (act)
-		closest_walk8<COUNT, 8, false>(S, (lds_u32 *)stk, S.ostk + (size_t)blockIdx.x * WAVE, (size_t)gridDim.x * WAVE, o,
-					       d, ob, inv, 0.f, false, tbest, hid, tc, at.x, at.y);
+		closest_walk8<COUNT, 8, false>(S, lane_stack<false>(S, stk), o, d, ob, inv, 0.f, false, tbest, hid, tc, at.x, at.y);
 }
 
 /* the closest-hit walk of this scene: the 8-wide tree when built and chosen (DScene.trace_w8) */
@@ -735,7 +677,6 @@ __device__ __forceinline__ void gi_batch_packed(const DScene &S, const DParams &
 						float *gp_tab, uint32_t *off, uint32_t ngi_mine, f3 &acc, TraceOut &T,
 						TraceCount &tc, u64 &n_closest, const TracePack<true> &pack)
 {
-	static_assert(!RTX_TRACE_CULL, "the queue does not carry the kept group's entry distance");
 	uint32_t total;
 	const uint32_t ex = wave_excl_scan(ngi_mine, &total);
 	if (total == 0)
@@ -825,9 +766,6 @@ template <> struct PrimaryRays<true> {
 };
 
 template <bool COUNT, bool LIST, bool PACK, bool RAYS = false>
-#ifndef RTX_TRACE_OCC
-#define RTX_TRACE_OCC 6 /* waves per SIMD k_trace is register-capped for (80 VGPRs; with 9 LDS stack entries, 24 waves per CU) */
-#endif
 __global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_trace(DScene S, DFrame F, DParams P, float *__restrict__ rgb,
 						float *__restrict__ zbuf, DTask *__restrict__ tasks, uint32_t task_cap,
 						float4 *__restrict__ staging, uint32_t staging_cap,
@@ -1120,387 +1058,10 @@ __global__ __launch_bounds__(WAVE) void k_accum(DFrame F, DParams P, const uint2
 }
 
 /* ------------------------------------------------------------------------ */
-/* k_rays: closest / any hit of a caller's ray batch (rtx_trace_rays*)      */
+/* the rest of this translation unit (one object: the device functions above are shared) */
 /* ------------------------------------------------------------------------ */
-/* Persistent waves, one per workgroup like k_trace (the closest walk's lane stack is per
- * workgroup: LDS, then DScene.ostk by blockIdx.x / gridDim.x, which the host sizes for THIS
- * grid), taking 64-ray packets from atomic counters, `grab` consecutive packets at a time.  A
- * walk of a packet is short next to a tile's ray trees, and one counter serves about 80 M
- * device-wide atomics a second (33 M rays took 6.5 ms whatever they hit; 1.2 ms with eight), so the packets are dealt
- * over `queues` counters on lines of their own: wave b takes from queue b % queues, which owns the
- * grabs j = queue + k * queues (an equal share, interleaved, for an equal share of the waves).  A ray is two float4 (rtx_ray: origin, tmax |
- * dir, pad), a hit two float4 (rtx_hit: t, object, material, outside | n, pad).  With perm (the
- * RTX_RAYS_REORDER sort's index list) lane i of a packet traces ray perm[i] and writes hit
- * perm[i]: a ray's result never depends on the rays it shares a wave with, as the closest t is
- * a minimum over accepted hits and the box tests only cull. */
-template <bool COUNT, bool ANY>
-__global__ __launch_bounds__(WAVE, RTX_TRACE_OCC) void k_rays(DScene S, const float4 *__restrict__ rays,
-							      float4 *__restrict__ hits, const uint32_t *__restrict__ perm,
-							      uint32_t n, uint32_t queues, uint32_t grab,
-							      unsigned long long *__restrict__ ctr)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-	uint32_t *stk = (uint32_t *)lds_raw;
-	const uint32_t packets = (uint32_t)(((uint64_t)n + WAVE - 1) / WAVE);
-	TraceCount tc = { 0, 0, 0, 0, 0 };
-	u64 n_hits = 0;
-	const uint32_t queue = blockIdx.x % queues;
-	unsigned long long *head = ctr + RTX_RQ_HEADS + (size_t)queue * RTX_RQ_HEAD_STRIDE;
-	uint64_t pk = 0, pk_end = 0;
-	for (;;) {
-		if (pk == pk_end) {
-			uint32_t k = 0;
-			if (lane_id() == 0)
-				k = (uint32_t)atomicAdd(head, 1ull);
-			k = uni(__shfl(k, 0, WAVE));
-			pk = ((uint64_t)k * queues + queue) * grab;
-			if (pk >= packets)
-				break;
-			pk_end = pk + grab < packets ? pk + grab : packets;
-		}
-		const uint64_t i = pk++ * WAVE + lane_id();
-		const bool act = i < n;
-		size_t idx = 0;
-		float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, 0.f);
-		if (act) {
-			idx = perm ? (size_t)perm[i] : (size_t)i;
-			r0 = rays[2 * idx];
-			r1 = rays[2 * idx + 1];
-		}
-		const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
-		float t = r0.w < FLT_MAX ? r0.w : FLT_MAX; /* tmax: INFINITY (or NaN) = the renderer's unbounded ray */
-		uint32_t hid;
-		lds_sync();
-		trace_closest<COUNT, ANY, true>(S, stk, act, o, d, RTX_NONE, t, hid, tc);
-		const bool hit = act && hid != RTX_NONE;
-		float4 h0 = make_float4(0.f, __uint_as_float(0xFFFFFFFFu), __uint_as_float(0xFFFFFFFFu), 0.f);
-		float4 h1 = make_float4(0.f, 0.f, 0.f, 0.f);
-		if (hit) {
-			const HitInfo h = hit_info(S, hid, o, d, t);
-			h0 = make_float4(t, __uint_as_float(h.obj), __uint_as_float(h.mat), __uint_as_float(h.outside ? 1u : 0u));
-			h1 = make_float4(h.n.x, h.n.y, h.n.z, 0.f);
-		}
-		if (act) {
-			hits[2 * idx] = h0;
-			hits[2 * idx + 1] = h1;
-		}
-		n_hits += popc64(ballot(hit));
-	}
-	if (COUNT) {
-		u64 a = tc.nodes, b = tc.tris, c = tc.sph, d2 = tc.pln, f = tc.far;
-#pragma unroll
-		for (int o2 = 32; o2 > 0; o2 >>= 1) {
-			a += __shfl_xor(a, o2, WAVE);
-			b += __shfl_xor(b, o2, WAVE);
-			c += __shfl_xor(c, o2, WAVE);
-			d2 += __shfl_xor(d2, o2, WAVE);
-			f += __shfl_xor(f, o2, WAVE);
-		}
-		if (lane_id() == 0) {
-			atomicAdd(&ctr[RTX_RQ_NODES], a);
-			atomicAdd(&ctr[RTX_RQ_TRIS], b);
-			atomicAdd(&ctr[RTX_RQ_SPHERES], c);
-			atomicAdd(&ctr[RTX_RQ_PLANES], d2);
-			atomicAdd(&ctr[RTX_RQ_FAR], f);
-		}
-	}
-	if (lane_id() == 0 && n_hits)
-		atomicAdd(&ctr[RTX_RQ_HITS], n_hits);
-}
-
-/* the W*H primary rays of a frame as rtx_ray records, row-major, tmax = INFINITY: k_trace's own rays */
-__global__ __launch_bounds__(256) void k_frame_rays(DFrame F, float4 *__restrict__ rays)
-{
-	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-	if (i >= (uint64_t)F.width * F.height)
-		return;
-	const uint32_t px = (uint32_t)(i % F.width), py = (uint32_t)(i / F.width);
-	const f3 o = ld3(F.origin);
-	f3 d;
-	RTX_PRIMARY_DIR(F, px, py, o, d);
-	rays[2 * i] = make_float4(o.x, o.y, o.z, INFINITY);
-	rays[2 * i + 1] = make_float4(d.x, d.y, d.z, 0.f);
-}
-
-__global__ void k_kat(int kind, uint32_t n, const float *__restrict__ in, float *__restrict__ out, int u32mode)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const int wi = rtx_kat_in_width[kind], wo = rtx_kat_out_width[kind];
-	const float *x = in + (size_t)i * wi;
-	float *y = out + (size_t)i * wo;
-	for (int k = 0; k < wo; k++)
-		y[k] = 0.f;
-	switch (kind) {
-	case RTX_KAT_MOLLER: {
-		float t = 0.f;
-		bool h = hit_triangle(ld3(x + 6), ld3(x + 9), ld3(x + 12), ld3(x), ld3(x + 3), x[15], t);
-		y[0] = h;
-		y[1] = h ? t : 0.f;
-	} break;
-	case RTX_KAT_SPHERE: {
-		float t = 0.f;
-		f3 o = ld3(x), d = ld3(x + 3), c = ld3(x + 6);
-		bool h = hit_sphere(c, x[9], o, d, x[10], t);
-		y[0] = h;
-		if (h) {
-			y[1] = t;
-			f3 n = mul3s(sub3(add3(mul3s(d, t), o), c), 1.f / x[9]);
-			y[2] = n.x;
-			y[3] = n.y;
-			y[4] = n.z;
-		}
-	} break;
-	case RTX_KAT_PLANE: {
-		float t = 0.f;
-		f3 o = ld3(x), d = ld3(x + 3), nn = ld3(x + 6);
-		bool h = hit_plane(nn, x[9], o, d, x[10], t);
-		y[0] = h;
-		if (h) {
-			y[1] = t;
-			f3 n = signbit(dot3(nn, d)) ? nn : mul3s(nn, -1.f);
-			y[2] = n.x;
-			y[3] = n.y;
-			y[4] = n.z;
-		}
-	} break;
-	case RTX_KAT_SLAB: {
-		float tmin = 0.f, tmax = 0.f;
-		bool h = slab_ref(ld3(x + 6), ld3(x + 9), x[12], ld3(x), ld3(x + 3), tmin, tmax);
-		y[0] = h;
-		y[1] = h ? tmin : 0.f;
-		y[2] = h ? tmax : 0.f;
-	} break;
-	case RTX_KAT_NOISE:
-		y[0] = simplex3(x[0], x[1], x[2]);
-		break;
-	case RTX_KAT_TEXTURE: {
-		DMaterial m;
-		m.tex = (int)x[0];
-		m.periodic = (int)x[1];
-		for (int k = 0; k < 3; k++) {
-			m.color[0][k] = x[2 + k];
-			m.color[1][k] = x[5 + k];
-		}
-		m.scale = x[8];
-		m.mortar = x[9];
-		m.nfs = x[10];
-		m.ns = x[11];
-		m.fs = x[12];
-		f3 c = texture_color(m, ld3(x + 13), u32mode);
-		y[0] = c.x;
-		y[1] = c.y;
-		y[2] = c.z;
-	} break;
-	case RTX_KAT_SPH_LIGHT:
-	case RTX_KAT_TRI_LIGHT: {
-		DEmitter e;
-		f3 p = mk3(0.f, 0.f, 0.f);
-		float u1, u2;
-		if (kind == RTX_KAT_SPH_LIGHT) {
-			e.type = RTX_SPHERE;
-			for (int k = 0; k < 3; k++)
-				e.p0[k] = x[k];
-			e.radius = x[3];
-			p = ld3(x + 4);
-			u1 = x[7];
-			u2 = x[8];
-		} else {
-			e.type = RTX_TRIANGLE;
-			for (int k = 0; k < 3; k++) {
-				e.p0[k] = x[k];
-				e.p1[k] = x[3 + k];
-				e.p2[k] = x[6 + k];
-			}
-			u1 = x[9];
-			u2 = x[10];
-		}
-		f3 l = light_point(e, p, u1, u2);
-		y[0] = l.x;
-		y[1] = l.y;
-		y[2] = l.z;
-	} break;
-	case RTX_KAT_MORTON: {
-		/* accel.c:72-88 (used by the reference's BVH build; kept for parity of the KAT suite) */
-		uint32_t c = 0;
-		for (int a = 0; a < 3; a++) {
-			uint32_t v = (uint32_t)(1023.f * x[a]);
-			v = (v * 0x00010001u) & 0xFF0000FFu;
-			v = (v * 0x00000101u) & 0x0F00F00Fu;
-			v = (v * 0x00000011u) & 0xC30C30C3u;
-			v = (v * 0x00000005u) & 0x49249249u;
-			c += v * (a == 0 ? 4u : a == 1 ? 2u : 1u);
-		}
-		y[0] = __uint_as_float(c);
-	} break;
-	case RTX_KAT_U32:
-		y[0] = __uint_as_float(to_u32(x[0], RTX_U32_SAT));
-		y[1] = __uint_as_float(to_u32(x[0], RTX_U32_WRAP));
-		break;
-	case RTX_KAT_GI_DIR: {
-		f3 dd = gi_direction(ld3(x), x[3], x[4], x[5]);
-		y[0] = dd.x;
-		y[1] = dd.y;
-		y[2] = dd.z;
-	} break;
-	case RTX_KAT_REFRACT: {
-		f3 dd = ld3(x), nn = ld3(x + 3);
-		float b = dot3(nn, dd);
-		f3 r = refract_dir(dd, nn, b, signbit(b), x[6]);
-		y[0] = r.x;
-		y[1] = r.y;
-		y[2] = r.z;
-	} break;
-	}
-}
-
-/* ------------------------------------------------------------------------ */
-/* launchers (declared in rtx_launch.h)                                     */
-/* ------------------------------------------------------------------------ */
-extern "C" size_t rtx_trace_lds_bytes(uint32_t stack_size)
-{
-	size_t pad = 0;
-#if RTX_MEASURE
-	/* RTX_TRACE_LDS_PAD (measurement builds): extra bytes per wave, to read k_trace's occupancy slope */
-	const char *e = getenv("RTX_TRACE_LDS_PAD");
-	pad = e ? (size_t)atoi(e) : 0;
-#endif
-	const size_t lstk = stack_size < RTX_TRACE_LSTK ? stack_size : RTX_TRACE_LSTK;
-	return (size_t)WAVE * SPW * 4 + 80 * 4 + lstk * WAVE * 4 + pad;
-}
-
-extern "C" size_t rtx_trace_pack_bytes(uint32_t pack_seg)
-{
-	return (size_t)pack_seg * RTX_PACK_BYTES;
-}
-
-extern "C" hipError_t rtx_trace_occupancy(uint32_t stack_size, int *blocks_per_cu)
-{
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_trace<false, false, false>, WAVE,
-							     rtx_trace_lds_bytes(stack_size));
-}
-
-extern "C" hipError_t rtx_launch_trace(const DScene *S, const DFrame *F, const DParams *P, float *rgb, float *z,
-				       DTask *tasks, uint32_t task_cap, float4 *staging, uint32_t staging_cap,
-				       float4 *sp_out, uint32_t sp_cap, uint2 *tile_rec, uint32_t tile_begin,
-				       uint32_t tile_end, unsigned long long *ctr, uint32_t waves, int count,
-				       const uint32_t *tile_list, void *pack, uint32_t pack_seg, const float4 *prim_rays,
-				       hipStream_t stream)
-{
-	const size_t lds = rtx_trace_lds_bytes(S->stack_size);
-	if (pack && (!S->trace_w8 || !pack_seg || pack_seg % WAVE)) /* the packed instances walk the 8-wide tree alone */
-		return hipErrorInvalidValue;
-	if (prim_rays) { /* a ray batch (rtx_render_rays*): the whole image or a shard, never a tile list */
-		if (tile_list)
-			return hipErrorInvalidValue;
-#define RTX_TRACE_LAUNCH_RAYS(C, K)                                                                                            \
-	hipLaunchKernelGGL((k_trace<C, false, K, true>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,       \
-			   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<true>{ prim_rays }, tile_rec, tile_begin,   \
-			   tile_end, ctr, TileList<false>{}, pk##K)
-		const TracePack<true> pktrue{ (unsigned char *)pack, pack_seg };
-		const TracePack<false> pkfalse{};
-		if (pack && count)
-			RTX_TRACE_LAUNCH_RAYS(true, true);
-		else if (pack)
-			RTX_TRACE_LAUNCH_RAYS(false, true);
-		else if (count)
-			RTX_TRACE_LAUNCH_RAYS(true, false);
-		else
-			RTX_TRACE_LAUNCH_RAYS(false, false);
-#undef RTX_TRACE_LAUNCH_RAYS
-		return hipGetLastError();
-	}
-#define RTX_TRACE_LAUNCH(C, L, ...)                                                                                            \
-	do {                                                                                                                    \
-		if (pack)                                                                                                       \
-			hipLaunchKernelGGL((k_trace<C, L, true>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks,  \
-					   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<false>{}, tile_rec,          \
-					   tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ },                                  \
-					   TracePack<true>{ (unsigned char *)pack, pack_seg });                                    \
-		else                                                                                                            \
-			hipLaunchKernelGGL((k_trace<C, L, false>), dim3(waves), dim3(WAVE), lds, stream, *S, *F, *P, rgb, z, tasks, \
-					   task_cap, staging, staging_cap, sp_out, sp_cap, PrimaryRays<false>{}, tile_rec,          \
-					   tile_begin, tile_end, ctr, TileList<L>{ __VA_ARGS__ }, TracePack<false>{});             \
-	} while (0)
-	if (tile_list && count)
-		RTX_TRACE_LAUNCH(true, true, tile_list);
-	else if (tile_list)
-		RTX_TRACE_LAUNCH(false, true, tile_list);
-	else if (count)
-		RTX_TRACE_LAUNCH(true, false);
-	else
-		RTX_TRACE_LAUNCH(false, false);
-#undef RTX_TRACE_LAUNCH
-	return hipGetLastError();
-}
-
-extern "C" hipError_t rtx_launch_accum(const DFrame *F, const DParams *P, const uint2 *tile_rec,
-				       const float4 *contrib, uint32_t tile_begin, uint32_t ntiles, float *rgb,
-				       const uint32_t *tile_list, hipStream_t stream)
-{
-	if (!ntiles || !rgb)
-		return hipSuccess;
-	if (tile_list)
-		hipLaunchKernelGGL(k_accum<true>, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb,
-				   TileList<true>{ tile_list });
-	else
-		hipLaunchKernelGGL(k_accum<false>, dim3(ntiles), dim3(WAVE), 0, stream, *F, *P, tile_rec, contrib, tile_begin, rgb,
-				   TileList<false>{});
-	return hipGetLastError();
-}
-
-/* k_rays keeps only the closest walk's LDS lane-stack entries */
-extern "C" size_t rtx_rays_lds_bytes(uint32_t stack_size)
-{
-	const size_t lstk = stack_size < RTX_TRACE_LSTK ? stack_size : RTX_TRACE_LSTK;
-	return lstk * WAVE * 4;
-}
-
-extern "C" hipError_t rtx_rays_occupancy(uint32_t stack_size, int *blocks_per_cu)
-{
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_rays<false, false>, WAVE,
-							     rtx_rays_lds_bytes(stack_size));
-}
-
-/* S->ostk must hold waves * 64 * (stack_size - RTX_TRACE_LSTK) entries: this launch's own grid */
-extern "C" hipError_t rtx_launch_rays(const DScene *S, const float4 *rays, float4 *hits, const uint32_t *perm, uint32_t n,
-				      uint32_t queues, uint32_t grab, unsigned long long *ctr, uint32_t waves, int count, int any,
-				      hipStream_t stream)
-{
-	const size_t lds = rtx_rays_lds_bytes(S->stack_size);
-#define RTX_RAYS_LAUNCH(C, A) \
-	hipLaunchKernelGGL((k_rays<C, A>), dim3(waves), dim3(WAVE), lds, stream, *S, rays, hits, perm, n, queues, grab, ctr)
-	if (count && any)
-		RTX_RAYS_LAUNCH(true, true);
-	else if (count)
-		RTX_RAYS_LAUNCH(true, false);
-	else if (any)
-		RTX_RAYS_LAUNCH(false, true);
-	else
-		RTX_RAYS_LAUNCH(false, false);
-#undef RTX_RAYS_LAUNCH
-	return hipGetLastError();
-}
-
-extern "C" hipError_t rtx_launch_frame_rays(const DFrame *F, float4 *rays, hipStream_t stream)
-{
-	const uint64_t n = (uint64_t)F->width * F->height;
-	hipLaunchKernelGGL(k_frame_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, *F, rays);
-	return hipGetLastError();
-}
-
-extern "C" hipError_t rtx_launch_kat(int kind, uint32_t n, const float *in, float *out, int u32mode,
-				     hipStream_t stream)
-{
-	hipLaunchKernelGGL(k_kat, dim3((n + 255) / 256), dim3(256), 0, stream, kind, n, in, out, u32mode);
-	return hipGetLastError();
-}
-
-/* the code object of this file on the current device, loaded now (rtx_open) rather than at the
- * first launch inside an upload or a render */
-extern "C" __attribute__((visibility("hidden"))) hipError_t rtx_load_trace(void)
-{
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *)k_accum<false>);
-}
+/* Nothing below is compiled into a k_trace or k_accum instance.  Each part relies on the code above, and is
+ * included here only. */
+#include "rtx_trace_rays.h"   /* k_rays, k_frame_rays: the ray queries */
+#include "rtx_trace_kat.h"    /* k_kat: the known-answer-test kernel */
+#include "rtx_trace_launch.h" /* the host launch code (rtx_launch.h) */

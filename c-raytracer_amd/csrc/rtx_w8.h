@@ -96,20 +96,11 @@ __device__ __forceinline__ bool w8_slab_tn(float lx, float hx, float ly, float h
 	tn_out = tn;
 	return tn <= tf;
 }
-template <int OCT>
+/* the generic octant's test without the entry distance (the any-hit walk) */
 __device__ __forceinline__ bool w8_slab(float lx, float hx, float ly, float hy, float lz, float hz, float tl)
 {
-	if (OCT == 8) {
-		const float tn = fmaxf(fmaxf(fminf(lx, hx), fminf(ly, hy)), fmaxf(fminf(lz, hz), 0.f));
-		const float tf = fminf(fminf(fmaxf(lx, hx), fmaxf(ly, hy)), fminf(fmaxf(lz, hz), tl));
-		return tn <= tf;
-	}
-	const float nx = (OCT & 1) ? lx : hx, fx = (OCT & 1) ? hx : lx;
-	const float ny = (OCT & 2) ? ly : hy, fy = (OCT & 2) ? hy : ly;
-	const float nz = (OCT & 4) ? lz : hz, fz = (OCT & 4) ? hz : lz;
-	const float tn = fmaxf(fmaxf(nx, ny), fmaxf(nz, 0.f));
-	float tf = fminf(fminf(fx, fy), fz);
-	asm("v_min_f32 %0, %0, %1" : "+v"(tf) : "v"(tl));
+	const float tn = fmaxf(fmaxf(fminf(lx, hx), fminf(ly, hy)), fmaxf(fminf(lz, hz), 0.f));
+	const float tf = fminf(fminf(fmaxf(lx, hx), fmaxf(ly, hy)), fminf(fmaxf(lz, hz), tl));
 	return tn <= tf;
 }
 /* The same test (OCT < 8) as a word whose sign bit says "miss": with A the entry (max of the near
@@ -136,13 +127,12 @@ template <int P> __device__ __forceinline__ uint32_t w8_miss_bit(uint32_t m)
 	return (m >> (31 - P)) & (1u << P);
 }
 
-template <int OCT, int C>
-__device__ __forceinline__ bool w8_child(const uint32_t (&w)[16], f3 s, f3 b, float tl)
+template <int C> __device__ __forceinline__ bool w8_child(const uint32_t (&w)[16], f3 s, f3 b, float tl)
 {
 	constexpr int W = C >> 2, B = C & 3;
-	return w8_slab<OCT>(fmaf(ubyte<B>(w[4 + W]), s.x, b.x), fmaf(ubyte<B>(w[6 + W]), s.x, b.x),
-			    fmaf(ubyte<B>(w[8 + W]), s.y, b.y), fmaf(ubyte<B>(w[10 + W]), s.y, b.y),
-			    fmaf(ubyte<B>(w[12 + W]), s.z, b.z), fmaf(ubyte<B>(w[14 + W]), s.z, b.z), tl);
+	return w8_slab(fmaf(ubyte<B>(w[4 + W]), s.x, b.x), fmaf(ubyte<B>(w[6 + W]), s.x, b.x),
+		       fmaf(ubyte<B>(w[8 + W]), s.y, b.y), fmaf(ubyte<B>(w[10 + W]), s.y, b.y),
+		       fmaf(ubyte<B>(w[12 + W]), s.z, b.z), fmaf(ubyte<B>(w[14 + W]), s.z, b.z), tl);
 }
 /* the scalar-path copy (rtx_device.h DW8S): child C's plane offsets, ready floats (the same
  * values the conversions above produce, so the results are bit-identical), one s_load_dwordx8 */
@@ -158,12 +148,11 @@ __device__ __forceinline__ f2v w8s_axis(float lo, float hi, float s, float b)
 	const f2v q = { lo, hi }, sv = { s, s }, bv = { b, b };
 	return __builtin_elementwise_fma(q, sv, bv);
 }
-template <int OCT, int C>
-__device__ __forceinline__ bool w8_child_s(const DW8S *n, f3 s, f3 b, float tl)
+template <int C> __device__ __forceinline__ bool w8_child_s(const DW8S *n, f3 s, f3 b, float tl)
 {
 	const f8v p = w8s_planes<C>(n);
 	const f2v tx = w8s_axis(p[0], p[1], s.x, b.x), ty = w8s_axis(p[2], p[3], s.y, b.y), tz = w8s_axis(p[4], p[5], s.z, b.z);
-	return w8_slab<OCT>(tx.x, tx.y, ty.x, ty.y, tz.x, tz.y, tl);
+	return w8_slab(tx.x, tx.y, ty.x, ty.y, tz.x, tz.y, tl);
 }
 
 /* the node frame of an 8-wide node: per-axis scale s = invq * 2^e and offset b = o * invq - oi */
@@ -183,14 +172,13 @@ __device__ __forceinline__ uint32_t w8_child_miss(const uint32_t (&w)[16], f3 s,
 				 fmaf(ubyte<B>(w[8 + W]), s.y, b.y), fmaf(ubyte<B>(w[10 + W]), s.y, b.y),
 				 fmaf(ubyte<B>(w[12 + W]), s.z, b.z), fmaf(ubyte<B>(w[14 + W]), s.z, b.z), tl);
 }
-#ifndef RTX_W8_SIGN
-#define RTX_W8_SIGN 1 /* k_shadow's octant-specialised box tests through miss words (w8_slab_miss) */
-#endif
-/* hit mask of an 8-wide node's children in visit order: bit p for slot p ^ K */
+/* hit mask of an 8-wide node's children in visit order: bit p for slot p ^ K.  The octant-specialised
+ * instances test through miss words (w8_slab_miss); the generic one (K = 0: slot order) masks the empty
+ * slots out, as the min/max form would turn an empty slot's box around */
 template <int OCT, uint32_t K>
 __device__ __forceinline__ uint32_t w8_hits(const uint32_t (&w)[16], f3 s, f3 b, float tl)
 {
-	if constexpr (OCT < 8 && RTX_W8_SIGN) {
+	if constexpr (OCT < 8) {
 		uint32_t m = w8_miss_bit<0 ^ K>(w8_child_miss<OCT, 0>(w, s, b, tl));
 		m |= w8_miss_bit<1 ^ K>(w8_child_miss<OCT, 1>(w, s, b, tl));
 		m |= w8_miss_bit<2 ^ K>(w8_child_miss<OCT, 2>(w, s, b, tl));
@@ -200,35 +188,36 @@ __device__ __forceinline__ uint32_t w8_hits(const uint32_t (&w)[16], f3 s, f3 b,
 		m |= w8_miss_bit<6 ^ K>(w8_child_miss<OCT, 6>(w, s, b, tl));
 		m |= w8_miss_bit<7 ^ K>(w8_child_miss<OCT, 7>(w, s, b, tl));
 		return m ^ 0xFFu;
+	} else {
+		static_assert(K == 0, "the generic octant visits in slot order");
+		uint32_t hm = 0;
+		hm |= w8_child<0>(w, s, b, tl) ? 1u << 0 : 0u;
+		hm |= w8_child<1>(w, s, b, tl) ? 1u << 1 : 0u;
+		hm |= w8_child<2>(w, s, b, tl) ? 1u << 2 : 0u;
+		hm |= w8_child<3>(w, s, b, tl) ? 1u << 3 : 0u;
+		hm |= w8_child<4>(w, s, b, tl) ? 1u << 4 : 0u;
+		hm |= w8_child<5>(w, s, b, tl) ? 1u << 5 : 0u;
+		hm |= w8_child<6>(w, s, b, tl) ? 1u << 6 : 0u;
+		hm |= w8_child<7>(w, s, b, tl) ? 1u << 7 : 0u;
+		return hm & w[3];
 	}
-	uint32_t hm = 0;
-	hm |= w8_child<OCT, 0>(w, s, b, tl) ? 1u << (0 ^ K) : 0u;
-	hm |= w8_child<OCT, 1>(w, s, b, tl) ? 1u << (1 ^ K) : 0u;
-	hm |= w8_child<OCT, 2>(w, s, b, tl) ? 1u << (2 ^ K) : 0u;
-	hm |= w8_child<OCT, 3>(w, s, b, tl) ? 1u << (3 ^ K) : 0u;
-	hm |= w8_child<OCT, 4>(w, s, b, tl) ? 1u << (4 ^ K) : 0u;
-	hm |= w8_child<OCT, 5>(w, s, b, tl) ? 1u << (5 ^ K) : 0u;
-	hm |= w8_child<OCT, 6>(w, s, b, tl) ? 1u << (6 ^ K) : 0u;
-	hm |= w8_child<OCT, 7>(w, s, b, tl) ? 1u << (7 ^ K) : 0u;
-	if (OCT == 8)
-		hm &= w[3]; /* K = 0: slot order; the min/max form would turn an empty slot's box around */
-	return hm;
 }
-#ifndef RTX_W8_SKIP
-#define RTX_W8_SKIP 1 /* scalar path: branch over the empty slots (the slot mask is wave-uniform): scene5 k_shadow 557 -> 548 ms, scene6 2739 -> 2721 ms */
-#endif
+/* the scalar path branches over the empty slots (the slot mask is wave-uniform; fixed: scene5 k_shadow
+ * 557 -> 548 ms, scene6 2739 -> 2721 ms) */
 template <int OCT, uint32_t K, int C>
 __device__ __forceinline__ uint32_t w8_hit_s(const DW8S *n, uint32_t w3, f3 s, f3 b, float tl)
 {
-	if (RTX_W8_SKIP && !((w3 >> C) & 1u))
+	if (!((w3 >> C) & 1u))
 		return 0u;
-	if constexpr (OCT < 8 && RTX_W8_SIGN) { /* the divergent path's miss-word form: the same bits */
+	if constexpr (OCT < 8) { /* the divergent path's miss-word form: the same bits */
 		const f8v p = w8s_planes<C>(n);
 		const f2v tx = w8s_axis(p[0], p[1], s.x, b.x), ty = w8s_axis(p[2], p[3], s.y, b.y), tz = w8s_axis(p[4], p[5], s.z, b.z);
 		const uint32_t m = w8_slab_miss<OCT>(tx.x, tx.y, ty.x, ty.y, tz.x, tz.y, tl);
 		return w8_miss_bit<C ^ K>(m) ^ (1u << (C ^ K));
+	} else {
+		static_assert(K == 0, "the generic octant visits in slot order");
+		return w8_child_s<C>(n, s, b, tl) ? 1u << C : 0u;
 	}
-	return w8_child_s<OCT, C>(n, s, b, tl) ? 1u << (C ^ K) : 0u;
 }
 template <int OCT, uint32_t K>
 __device__ __forceinline__ uint32_t w8_hits_s(const DW8S *q, uint32_t w3, f3 s, f3 b, float tl)
@@ -242,18 +231,12 @@ __device__ __forceinline__ uint32_t w8_hits_s(const DW8S *q, uint32_t w3, f3 s, 
 	hm |= w8_hit_s<OCT, K, 5>(q, w3, s, b, tl);
 	hm |= w8_hit_s<OCT, K, 6>(q, w3, s, b, tl);
 	hm |= w8_hit_s<OCT, K, 7>(q, w3, s, b, tl);
-	if (OCT == 8 && !RTX_W8_SKIP)
-		hm &= w3;
 	return hm;
 }
 
-#ifndef RTX_W8_ORDER
-#define RTX_W8_ORDER 1 /* closest hits (k_trace): visit hit children in the octant's slot order (0: plain slot order) */
-#endif
-#ifndef RTX_W8_SORDER
-#define RTX_W8_SORDER 0 /* any-hit (k_shadow): the octant's slot order; plain slot order saves the mask permutes */
-#endif
-
+/* The visit order K of hit children is fixed per walk: the closest-hit walk (k_trace) takes the octant's
+ * slot order, K = ~OCT & 7; the any-hit walk (k_shadow) plain slot order, K = 0, which saves the mask
+ * permutes (scene5 k_shadow 547 -> 537 ms, scene6 2724 -> 2703 ms). */
 /* one 8-wide node visit's box tests: the hit mask in visit order and the node's masks */
 struct W8Visit {
 	uint32_t hm, base, io, to, nv;
@@ -296,8 +279,7 @@ __device__ __forceinline__ W8Visit w8_visit_s(const DW8S *n, f3 invq, f3 oi, flo
 
 /* closest-hit visits (k_trace) with entry distances: besides the hit mask, the nearest hit inner
  * child (slot in visit order, or 8 for none) and the least entry distance of the hit inner
- * children (a lower bound for every sibling kept for later: RTX_TRACE_CULL drops a kept group
- * whose bound the closest hit so far has passed) */
+ * children (a lower bound for every sibling kept for later) */
 struct W8VisitT {
 	W8Visit v;
 	uint32_t near;
@@ -307,7 +289,7 @@ template <int OCT, uint32_t K, int C, bool SC>
 __device__ __forceinline__ void w8_child_t(const uint32_t *w, f3 s, f3 b, float tl, uint32_t io, uint32_t &hm, uint32_t &near,
 					   float &tin)
 {
-	if (SC && RTX_W8_SKIP && !(((io >> 8) >> C) & 1u)) /* an empty slot (wave-uniform on the scalar path) */
+	if (SC && !(((io >> 8) >> C) & 1u)) /* an empty slot (wave-uniform on the scalar path) */
 		return;
 	float t[6];
 	if (SC) { /* w: the scalar-path copy (DW8S) */

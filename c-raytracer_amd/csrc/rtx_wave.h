@@ -1,6 +1,6 @@
 /*
  * Wavefront helpers and the shade-point record shared by the gfx950 kernels
- * (rtx_trace.hip: k_trace / k_accum / k_kat, rtx_shadow.hip: k_shadow).
+ * (rtx_trace.hip and its parts: k_trace / k_accum / k_kat, rtx_shadow.hip: k_shadow).
  * One wavefront = 64 lanes; every reduction here runs in a fixed lane order,
  * so sums are bit-identical whichever wave or GPU computes them.
  */

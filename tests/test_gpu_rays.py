@@ -1,4 +1,4 @@
-"""Ray queries (rtx_trace_rays*, k_rays in csrc/rtx_trace.hip) on the GPU.
+"""Ray queries (rtx_trace_rays*, k_rays in csrc/rtx_trace_rays.h) on the GPU.
 
 A frame is an origin plus a grid of targets, so the same pencil of rays can be traced three ways:
 by the renderer (its z buffer), by a closest query of rtx_frame_rays_device's rays, and by the

@@ -901,7 +901,7 @@ int main(int argc, char **argv)
 				}
 				lane_tl[l] = dist;
 				/* W8SIM_ORDER: 0 front to back from the shade point (octant order), 1 plain slot order
-				 * (k_shadow's RTX_W8_SORDER 0), 2 back to front (front to back from the light) */
+				 * (k_shadow's, fixed: the other two measured no faster), 2 back to front (front to back from the light) */
 				const uint32_t K = order == 1 ? 0u : order == 2 ? (uint32_t)oct & 7u : ~(uint32_t)oct & 7u;
 				/* the walk: node, group register, stack; leaf hits counted per visit */
 				std::vector<uint32_t> stk;
